@@ -7,6 +7,11 @@ Workload: the 256^3 structural lattice x 20 substeps (BASELINE.json:9, the confi
 --gpus N > 1 the SAME 256^3 mesh is split spatially over N ranks (BASELINE.json:10) => strong scaling.
 `--n 64` runs config[1] instead.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what its headline figure needs: set-up, W untimed ticks, the K timed
+ticks, the outputs (--dump-outputs DIR: positions and velocities after the last timed tick) and the line (`value` = particle-substeps/s
+over the timed ticks, `ms_per_step` = their wall time / K). Everything described below beside that -- self-verification, roofline,
+the card's clocks and power, CPU baseline, sustained leg, the N > 1 exchange timing and A/B variants -- runs with --full.
+
 Launch: `python bench.py` (N=1) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
  bench.py --gpus N --steps K --warmup W` — one process per GPU. torch.distributed (gloo) carries only the
@@ -203,7 +208,23 @@ def parse_args():
     ap.add_argument("--loopback-world", type=int, default=0,
                     help="diagnostic: run as rank 0 of this many ranks with SB_TEST_LOOPBACK (RCCL self-exchange on one GPU); "
                          "the reported value counts only the particles this rank owns")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the self-verification legs, the roofline block (per-kernel timing), the "
+                         "card's clocks and power, the CPU baseline, the sustained leg and (N > 1) the exchange timing and the A/B variants; "
+                         "the --no-* options switch single legs off again. Without it a run sets up, warms up, times --steps ticks, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed ticks, write what the last of them left a caller (sb_get_positions / sb_get_velocities of the whole "
+                         "cube, mesh order, float32) as DIR/positions.npy and DIR/velocities.npy; cubes of more than 2^21 particles as a "
+                         "fixed sample of them (seed 0, ascending particle ids)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.loopback_world > 1:
+        ap.error("--dump-outputs needs the whole cube: not with --loopback-world (one rank of several)")
+    if not args.full:       # a plain run: only what the headline figure needs
+        args.no_parity = args.no_cpu_baseline = args.no_sustained = args.no_gpu_state = args.no_ab = True
+    return args
 
 
 class LastWords:
@@ -513,6 +534,8 @@ def run_variant(ctx, name, transport, schedule, steps, warmup, is_default):
             sampler = GpuStateSampler(_pci_bus_id(ctx["torch"], ctx["device"]) if ctx["n_dev"] > 0 else None).start()
         elapsed, ev_ms = timed_region(ctx, sb, warmup, steps)
         gpu_state = sampler.stop() if sampler is not None else None
+        if is_default and args.dump_outputs:      # (the variant whose figure the line carries; a later one overwrites an earlier)
+            dump_outputs(ctx, sb, args.dump_outputs)
         N = args.n ** 3
         rec.update({"steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps, "value": N * args.substeps * steps / elapsed,
                     "tick_ms_hip_events_rank0": ev_ms / steps})
@@ -524,7 +547,7 @@ def run_variant(ctx, name, transport, schedule, steps, warmup, is_default):
             rec["finite"] = finite
         else:
             g, finite = None, None
-        ex = exchange_leg(ctx, sb)
+        ex = exchange_leg(ctx, sb) if args.full else None
         if ctx["dist"] is not None:
             allx = [None] * world
             ctx["dist"].all_gather_object(allx, ex)
@@ -560,7 +583,7 @@ def full_variant(ctx, name, transport, schedule, with_sustained, runtime):
     sb, stats = res["sb"], res["stats"]
     setup_s = time.time() - ctx["t_setup"]
     # per-kernel HIP-event timing on the solver's stream: two extra eager ticks, outside the timed region
-    slot_ms, slot_cnt = profiled_ticks(sb, 2)
+    slot_ms, slot_cnt = profiled_ticks(sb, 2) if args.full else (None, None)
     parity = {"ticks": res["calib"] + args.warmup + args.steps}
     if res["golden"] is not None:
         parity["golden"] = res["golden"]
@@ -568,7 +591,9 @@ def full_variant(ctx, name, transport, schedule, with_sustained, runtime):
         rep = sb.validate()
         parity["tables"] = {"constraints_checked": rep["constraints_checked"], "tiles_checked": rep["tiles_checked"], "errors": rep["errors"],
                             "clean": rep["errors"] == [0] * 6}
-    finite = res["finite"] if res["finite"] is not None else bool(np.isfinite(sb.get_positions()[sb.owner() == rank]).all())
+    finite = res["finite"]
+    if finite is None and args.full:
+        finite = bool(np.isfinite(sb.get_positions()[sb.owner() == rank]).all())
     parity["finite"] = finite
     per_rank = [None] * world
     dist.all_gather_object(per_rank, {"rank": rank, "owned": stats["n_particles_owned"], "ghosts": stats["n_particles_local"] - stats["n_particles_owned"],
@@ -578,7 +603,10 @@ def full_variant(ctx, name, transport, schedule, with_sustained, runtime):
     sustained = sustained_leg(ctx, sb, rec["ms_per_step"]) if with_sustained else None
     out = None
     if rank == 0:
-        out = build_line(ctx, sb, stats, res["elapsed"], res["ev_ms"], slot_ms, slot_cnt, parity, finite, res["gpu_state"], runtime, setup_s, False, N, M)
+        if args.full:
+            out = build_line(ctx, sb, stats, res["elapsed"], res["ev_ms"], slot_ms, slot_cnt, parity, finite, res["gpu_state"], runtime, setup_s, False, N, M)
+        else:
+            out = headline_line(ctx, stats, res["elapsed"], runtime, setup_s, False, N, M)
         out["config"]["halo_transport"] = transport
         if args.rccl_stand_in:
             out["config"]["rccl_stand_in"] = f"TEST RUN: the variants named rccl/* ran over the {args.rccl_stand_in} transport (one-GPU box); not a measurement of RCCL"
@@ -671,6 +699,43 @@ def multi_rank(ctx, real_stdout):
     return out
 
 
+DUMP_PARTICLES = 1 << 21       # --dump-outputs: 2 arrays x 2^21 particles x 12 B = 48 MiB at most
+
+
+def dump_outputs(ctx, sb, out_dir):
+    """--dump-outputs: the positions and velocities the timed ticks left -- what sb_get_positions / sb_get_velocities hand a caller --
+    of the whole cube in the mesh's particle order, float32 (n, 3), as out_dir/positions.npy and out_dir/velocities.npy. A cube of more
+    than DUMP_PARTICLES particles is written as the same sample of them every run (seed 0, ascending particle ids). N > 1: every rank
+    contributes the particles it owns, rank 0 writes."""
+    args, rank, dist, mesh = ctx["args"], ctx["rank"], ctx["dist"], ctx["mesh"]
+    N = args.n ** 3
+    sample = None if N <= DUMP_PARTICLES else np.sort(np.random.default_rng(0).choice(N, DUMP_PARTICLES, replace=False))
+    owned = np.nonzero(sb.owner() == rank)[0]
+    gid = (mesh.global_id[owned] if ctx["sharded"] else owned).astype(np.int64)
+    x, v = sb.get_positions()[owned], sb.get_velocities()[owned]
+    if sample is None:
+        slot = gid
+    else:
+        slot = np.minimum(np.searchsorted(sample, gid), len(sample) - 1)
+        keep = sample[slot] == gid
+        slot, x, v = slot[keep], x[keep], v[keep]
+    parts = [(slot, x, v)]
+    if dist is not None:
+        parts = [None] * ctx["world"] if rank == 0 else None
+        dist.gather_object((slot, x, v), parts, dst=0)
+    if rank != 0:
+        return
+    n_out = N if sample is None else len(sample)
+    X = np.full((n_out, 3), np.nan, np.float32)
+    V = np.full((n_out, 3), np.nan, np.float32)
+    for s_, x_, v_ in parts:
+        X[s_] = x_
+        V[s_] = v_
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "positions.npy"), X)
+    np.save(os.path.join(out_dir, "velocities.npy"), V)
+
+
 def profiled_ticks(sb, prof_ticks=2):
     slot_ms = None
     for _ in range(prof_ticks):
@@ -702,6 +767,13 @@ def single_rank(ctx):
             sampler = GpuStateSampler(_pci_bus_id(torch, ctx["device"]) if ctx["n_dev"] > 0 else None).start()
         elapsed, ev_ms = timed_region(ctx, sb, args.warmup, args.steps)
         gpu_state = sampler.stop() if sampler is not None else None
+        if args.dump_outputs:
+            dump_outputs(ctx, sb, args.dump_outputs)
+        if loopback:
+            N = int(stats["n_particles_owned"])      # diagnostic mode: only this rank's share is simulated
+        if not args.full:
+            out = headline_line(ctx, stats, elapsed, runtime, setup_s, loopback, N, M)
+            return out
 
         # ---- self-verification, leg 1: the state the timed run ended with, against the oracle's golden checksum ------
         total_ticks = args.warmup + args.steps
@@ -717,8 +789,6 @@ def single_rank(ctx):
             parity["tables"] = {"constraints_checked": rep["constraints_checked"], "tiles_checked": rep["tiles_checked"], "errors": rep["errors"],
                                 "clean": rep["errors"] == [0] * 6}
         slot_ms, slot_cnt = profiled_ticks(sb, 2)
-        if loopback:
-            N = int(stats["n_particles_owned"])      # diagnostic mode: only this rank's share is simulated
         out = build_line(ctx, sb, stats, elapsed, ev_ms, slot_ms, slot_cnt, parity, finite, gpu_state, runtime, setup_s, loopback, N, M)
         if loopback:
             out["config"]["halo_transport"] = args.transport
@@ -740,11 +810,33 @@ def single_rank(ctx):
     return out
 
 
-def build_line(ctx, sb, stats, elapsed, ev_ms, slot_ms, slot_cnt, parity, finite, gpu_state, runtime, setup_s, loopback, N, M):
-    """The JSON line of the contract from one measured solver (rank 0)."""
+def headline_line(ctx, stats, elapsed, runtime, setup_s, loopback, N, M):
+    """The JSON line of the contract as a plain run prints it (rank 0): the headline figure and what it was measured on."""
     args, world, sharded = ctx["args"], ctx["world"], ctx["sharded"]
     value = N * args.substeps * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    mesh_s = ctx["mesh_s"]
+    return {
+        "metric": "particle-substeps/sec", "value": value, "unit": "particle-substeps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.n}^3 jelly cube, structural springs (N={N}, M={M}), {args.substeps} substeps/tick, "
+                               f"dt=0.02, explicit index-array graph, tile_particles={args.tile}" +
+                               (", HETEROGENEOUS masses and rest lengths (4-byte inverse masses, 8-byte constraint slots)" if args.heterogeneous else ""),
+                   "partition": "x".join(str(d) for d in _dims(world)), "graph_replay": (not args.no_graph) and (world == 1 or stats["halo_schedule"] in (2, 4)),
+                   "authoring": ("sharded: each rank hands over and plans its window only (sb_set_domain)" if sharded else "whole mesh on every rank"),
+                   "halo_transport": None,
+                   "halo_schedule": SCHEDULE_NAMES.get(stats["halo_schedule"]) if (world > 1 or loopback) else None,
+                   "runtime": runtime, "full": bool(args.full)},
+        "setup_seconds": setup_s, "setup_breakdown": {"mesh_generation": mesh_s, "Start (author + plan + upload)": setup_s - mesh_s},
+        "plan": stats,
+    }
+
+
+def build_line(ctx, sb, stats, elapsed, ev_ms, slot_ms, slot_cnt, parity, finite, gpu_state, runtime, setup_s, loopback, N, M):
+    """The JSON line of the contract from one measured solver (rank 0), as --full prints it: the headline line + self-verification + roofline."""
+    args, world = ctx["args"], ctx["world"]
+    value = N * args.substeps * args.steps / elapsed
     G = stats["n_global_colours"]
     owned = stats["n_particles_owned"]
     names = ["tile_kernel<1> on T0 (rounds + collide/velocity/integrate + rounds)",
@@ -820,21 +912,9 @@ def build_line(ctx, sb, stats, elapsed, ev_ms, slot_ms, slot_cnt, parity, finite
     alg_rate = alg_bytes[k_dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
     job_alg = b_alg(N, M) * value / N   # algorithmic B/s of the whole job
     parity["finite"] = finite
-    mesh_s = ctx["mesh_s"]
-    return {
-        "metric": "particle-substeps/sec", "value": value, "unit": "particle-substeps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.n}^3 jelly cube, structural springs (N={N}, M={M}), {args.substeps} substeps/tick, "
-                               f"dt=0.02, explicit index-array graph, tile_particles={args.tile}" +
-                               (", HETEROGENEOUS masses and rest lengths (4-byte inverse masses, 8-byte constraint slots)" if args.heterogeneous else ""),
-                   "partition": "x".join(str(d) for d in _dims(world)), "graph_replay": (not args.no_graph) and (world == 1 or stats["halo_schedule"] in (2, 4)),
-                   "authoring": ("sharded: each rank hands over and plans its window only (sb_set_domain)" if sharded else "whole mesh on every rank"),
-                   "halo_transport": None,
-                   "halo_schedule": SCHEDULE_NAMES.get(stats["halo_schedule"]) if (world > 1 or loopback) else None,
-                   "runtime": runtime, "gpu_state": gpu_state,
-                   "finite": finite, "parity": parity},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+    out = headline_line(ctx, stats, elapsed, runtime, setup_s, loopback, N, M)
+    out["config"].update({"gpu_state": gpu_state, "finite": finite, "parity": parity})
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": achieved / (HBM_PEAK / 1e9), "traffic": traffic,
                      "traffic_source": traffic_src or "none for this configuration: achieved/frac use the compulsory-bytes model",
                      "traffic_measured_on": traffic_meta,
@@ -856,10 +936,8 @@ def build_line(ctx, sb, stats, elapsed, ev_ms, slot_ms, slot_cnt, parity, finite
                      "B_alg_per_particle_substep": b_alg(N, M) / N,
                      "tick_ms_hip_events": ev_ms / args.steps,
                      "per_slot_ms_per_tick": {names[k]: float(slot_ms[k]) for k in range(len(names))},
-                     "per_slot_launches_per_tick": {names[k]: int(slot_cnt[k]) for k in range(len(names))}},
-        "setup_seconds": setup_s, "setup_breakdown": {"mesh_generation": mesh_s, "Start (author + plan + upload)": setup_s - mesh_s},
-        "plan": stats,
-    }
+                     "per_slot_launches_per_tick": {names[k]: int(slot_cnt[k]) for k in range(len(names))}}
+    return out
 
 
 def _dims(world):

@@ -8,12 +8,15 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# group scenarios put up to 8 ranks of one process on one device: the peer transport's waiting kernels need a hardware queue per rank,
+# and the launch environment's own GPU_MAX_HW_QUEUES (which the script only defaults) may be smaller
+ENV = dict(os.environ, GPU_MAX_HW_QUEUES="16")
 
 
 @pytest.mark.gpu
 def test_fixed_slice_of_the_fuzzer_is_bitwise():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_parity.py"), "--seed", "0", "--max", "160", "--seconds", "400"],
-                       capture_output=True, text=True, timeout=600)
+                       capture_output=True, text=True, timeout=600, env=ENV)
     lines = r.stdout.splitlines()
     summary = [l for l in lines if l.startswith("SUMMARY")]
     bad = [l for l in lines if l.split(" ", 1)[0] in ("MISMATCH", "ERROR", "CRASH")]
@@ -30,7 +33,7 @@ def test_seeds_that_once_failed(seed):
     """2005569: particles on a line through sb_group_* on 4 ranks under the block partition -- the windows' pair hashes agree, yet ONE window holds
     a leftover (T2) layer and the others none: tick programs of different shape (the mailbox layout follows the number of halo slots). The
     agreement now carries the shape; the group falls back to the whole mesh."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_parity.py"), "--only", str(seed)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_parity.py"), "--only", str(seed)], capture_output=True, text=True, timeout=300, env=ENV)
     assert r.returncode == 0 and "SUMMARY 1 scenarios: OK 1" in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
 
 

@@ -6,4 +6,4 @@
 N=${1:-4}; shift
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) \
-    bench.py --gpus $N --transport peer --steps 5 --warmup 2 "$@"
+    bench.py --full --gpus $N --transport peer --steps 5 --warmup 2 "$@"

@@ -3,16 +3,17 @@
 # same tick count: the order-independent state checksum must be identical (bench.py config.parity.golden.checksum).
 # usage on the GPU box: bash tools/multiproc_soak.sh
 R=$GRAFT_REPO_ROOT
+RESULTS=${RESULTS:-bench_out}; mkdir -p "$R/$RESULTS"      # the runs' lines and logs, under the repository root
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
-OUT=$R/gpurun_out/multiproc_soak.txt
+OUT=$R/$RESULTS/multiproc_soak.txt
 : > $OUT
 run() { # edge ticks procs extra
   local n=$1 t=$2 p=$3; shift 3
   if [ $p -eq 1 ]; then
-    timeout -k 10 500 python $R/bench.py --n $n --steps $t --warmup 2 --no-cpu-baseline --no-sustained "$@" 2>/dev/null
+    timeout -k 10 500 python $R/bench.py --full --n $n --steps $t --warmup 2 --no-cpu-baseline --no-sustained "$@" 2>/dev/null
   else
     timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $p --master-addr 127.0.0.1 --master-port $((29650 + p)) \
-      $R/bench.py --gpus $p --transport peer --no-ab --no-sustained --cube-edge $n --steps $t --warmup 2 "$@" 2>/dev/null
+      $R/bench.py --full --gpus $p --transport peer --no-ab --no-sustained --cube-edge $n --steps $t --warmup 2 "$@" 2>/dev/null
   fi | python -c "
 import json,sys
 j=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

@@ -3,12 +3,13 @@
 # 8-byte wide-packed slots of round 4 the two forms tie at 176^3 (10 648 tiles, profiles/r04u_width_quantisation_ab.txt): where do they part
 # above it? 128-lane (default) against 256-lane (SB_NARROW_MIN_TILES above the tile count) at 192^3 .. 256^3, interleaved, two repeats.
 R=$GRAFT_REPO_ROOT; cd $R
-OUT=gpurun_out/${1:-r04w}_width_large_ab.txt; : > $OUT
+RESULTS=${RESULTS:-bench_out}; mkdir -p "$R/$RESULTS"      # the runs' lines and logs, under the repository root
+OUT=$RESULTS/${1:-r04w}_width_large_ab.txt; : > $OUT
 for rep in 0 1; do
 for n in 192 224 256; do
   for v in narrow wide; do
     if [ $v = wide ]; then export SB_NARROW_MIN_TILES=1000000; else unset SB_NARROW_MIN_TILES; fi
-    python bench.py --n $n --steps 60 --warmup 10 --no-cpu-baseline --no-parity --no-sustained --no-gpu-state 2>/dev/null | python -c "
+    python bench.py --full --n $n --steps 60 --warmup 10 --no-cpu-baseline --no-parity --no-sustained --no-gpu-state 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read()); r = j['roofline']; p = j['plan']
 slots = r['per_slot_ms_per_tick']; cnt = r['per_slot_launches_per_tick']

@@ -3,11 +3,12 @@
 # workgroups fit the chip at once, 4 481 is two rounds and a fifth): per-launch times of the T0 and T1 kernels for 256-lane (default in this
 # range) against 128-lane workgroups (3 072 at once, each slower) over cube sizes whose tile counts fall on either side of the steps.
 R=$GRAFT_REPO_ROOT; cd $R
-OUT=gpurun_out/${1:-r04u}_width_quantisation_ab.txt; : > $OUT
+RESULTS=${RESULTS:-bench_out}; mkdir -p "$R/$RESULTS"      # the runs' lines and logs, under the repository root
+OUT=$RESULTS/${1:-r04u}_width_quantisation_ab.txt; : > $OUT
 for n in 96 104 112 120 128 136 144 152 160 176; do
   for v in wide narrow; do
     if [ $v = narrow ]; then export SB_NARROW_MIN_TILES=1; else unset SB_NARROW_MIN_TILES; fi
-    python bench.py --n $n --steps 200 --warmup 20 --no-cpu-baseline --no-parity --no-sustained --no-gpu-state 2>/dev/null | python -c "
+    python bench.py --full --n $n --steps 200 --warmup 20 --no-cpu-baseline --no-parity --no-sustained --no-gpu-state 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read()); r = j['roofline']; p = j['plan']
 slots = r['per_slot_ms_per_tick']; cnt = r['per_slot_launches_per_tick']
