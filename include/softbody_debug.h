@@ -39,6 +39,7 @@ extern "C" {
 #define SB_TUNE_NO_WIDE_SLOTS     (1u << 12)  /* 256-lane launches stage their slots through LDS (no 8-byte packed words) */
 #define SB_TUNE_AUTO_PREFER_OVERLAP (1u << 13) /* SB_SCHEDULE_AUTO's calibration decides for the overlapped schedule whatever it measured (tests) */
 #define SB_TUNE_NO_AUTO_CALIBRATION (1u << 14) /* SB_SCHEDULE_AUTO = SB_SCHEDULE_SERIAL_EAGER without measuring */
+#define SB_TUNE_NO_SHARED_PROGRAMS (1u << 15)  /* one copy of the constraint program per tile (tiles with identical programs do not share one) */
 typedef struct {
     uint32_t flags;                    /* SB_TUNE_* */
     int32_t tile_lanes;                /* 0 = by launch size; 128 | 256 | 512 forces the workgroup width of small spring tiles */

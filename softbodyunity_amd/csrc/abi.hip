@@ -65,7 +65,7 @@ void sb_tuning_default(sb_tuning *t) {
 int sb_set_tuning(sb_solver *s, const sb_tuning *t) {
     if (!s || !t) return fail(SB_ERR_INVALID_ARG, "sb_set_tuning: null argument");
     if (s->finalized) return fail(SB_ERR_STATE, "sb_set_tuning after sb_finalize");
-    constexpr uint32_t kAll = (SB_TUNE_NO_AUTO_CALIBRATION << 1) - 1u;
+    constexpr uint32_t kAll = (SB_TUNE_NO_SHARED_PROGRAMS << 1) - 1u;
     if (t->flags & ~kAll) return fail(SB_ERR_INVALID_ARG, "sb_set_tuning: unknown bit in flags");
     for (int32_t r : t->reserved) if (r) return fail(SB_ERR_INVALID_ARG, "sb_set_tuning: reserved fields must be 0 (sb_tuning_default)");
     if (t->tile_lanes != 0 && t->tile_lanes != 128 && t->tile_lanes != 256 && t->tile_lanes != 512) return fail(SB_ERR_INVALID_ARG, "sb_set_tuning: tile_lanes must be 0, 128, 256 or 512");
@@ -482,10 +482,17 @@ int finalize_link(sb_solver *s) {
             }
             // otherwise (no communicator) the host connects the mailboxes: sb_peer_mailbox_handle / sb_peer_connect, or the group does
         }
-        if (std::getenv("SB_PRINT_ALLOC"))       // diagnosis (printing only): where the arrays landed (run-to-run timing modes)
+        if (std::getenv("SB_PRINT_ALLOC")) {     // diagnosis (printing only): where the arrays landed (run-to-run timing modes)
             std::fprintf(stderr, "[alloc] pos3 %p prev %p vel %p wf %p w8 %p T0.stream %p T1.stream %p T0.tiles %p T1.tiles %p\n", (void *)s->d_pos3.p, (void *)s->d_prev.p,
                          (void *)s->d_vel.p, (void *)s->d_wf.p, (void *)s->d_w8.p, (void *)s->tiling[0].stream.p, (void *)s->tiling[1].stream.p,
                          (void *)s->tiling[0].tiles.p, (void *)s->tiling[1].tiles.p);
+            for (int tl = 0; tl < 3; ++tl) {     // tiles, distinct programs, bytes the tiles read / bytes uploaded (shared programs)
+                const DevTiling &D = s->tiling[tl];
+                if (D.n_tiles)
+                    std::fprintf(stderr, "[alloc] T%d: %d tiles, %lld distinct programs, stream %lld B read by the tiles, %lld B uploaded\n", tl, D.n_tiles,
+                                 (long long)D.n_programs, (long long)D.stream_bytes, (long long)(D.stream.count * sizeof(uint32_t)));
+            }
+        }
         HIP_CHECK(hipDeviceSynchronize());
         // authoring copies are no longer needed (keep rest values out of memory for 50M-constraint meshes)
         std::vector<float>().swap(s->pos); std::vector<float>().swap(s->vel); std::vector<float>().swap(s->rest);

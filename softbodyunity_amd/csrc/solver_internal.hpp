@@ -119,7 +119,8 @@ struct DevTiling {
     size_t lds_bytes = 0;
     int64_t n_slots = 0;         // constraints stored in the tile streams
     int64_t staged_particles = 0;   // sum of n_local over the device tiles
-    int64_t stream_bytes = 0;    // bytes of the tile streams (round words, palettes, slots)
+    int64_t stream_bytes = 0;    // bytes of the tile streams (round words, palettes, slots) the tiles read: sum of s_len x 4, shared programs counted per tile
+    int64_t n_programs = 0;      // distinct programs held in `stream` (tiles with identical programs share one copy; stream.count x 4 = bytes uploaded)
     int32_t max_local = 0, win_dwords = 4, pal_dwords = 0, rounds_dwords = 0;
     int32_t n_boundary = 0;      // world > 1: T0 -- the FIRST n_boundary tiles hold every particle some peer needs; T1 -- the LAST
                                  // n_boundary tiles hold every ghost and every sent particle

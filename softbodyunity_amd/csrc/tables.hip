@@ -531,6 +531,67 @@ void build_device(sb_solver *s) {
                 Piece().tiles.swap(Q.tiles); std::vector<uint32_t>().swap(Q.stream);
             }
         }
+        // Content-addressed programs. A tile's program (round words, palette, wave items, slots) is written in tile-local numbering, so
+        // tiles of the same shape run byte-identical programs: every interior tile of a lattice, and the face, edge and corner tiles of
+        // each kind. Keep ONE copy of each distinct program and point every descriptor that uses it at that copy; the descriptors keep
+        // their own s_hdr, s_len, n_rounds, n_pal and wave items, and the kernels and the validator reach a program only through
+        // s_begin. Programs used by more than one tile go first: the few KiB a launch then reads over and over stay in the L2 of every
+        // XCD, and a launch reads from HBM little more than the particle state. Only now, with every piece placed in one stream, can
+        // programs built by different host threads be compared. stream_bytes stays what the tiles READ (the sum of s_len x 4: the
+        // compulsory-bytes model of sb_stats.launch_bytes); what is uploaded is stream.count.
+        D.stream_bytes = (int64_t)stream.size() * 4;
+        D.n_programs = (int64_t)tiles.size();
+        if (!(s->tune_flags & SB_TUNE_NO_SHARED_PROGRAMS) && tiles.size() > 1) {
+            const size_t nt = tiles.size();
+            std::vector<uint64_t> key(nt);
+            sbp::parallel_for_chunks((int64_t)nt, 1024, [&](int64_t, int64_t tb, int64_t te) {
+                for (int64_t t = tb; t < te; ++t) {     // 64-bit FNV-1a over the header fields and the program's dwords
+                    const sbk::TileDesc &td = tiles[(size_t)t];
+                    if (td.s_len & 3u) throw std::runtime_error("internal: tile stream not 16-byte aligned");
+                    uint64_t h = 1469598103934665603ull;
+                    h = (h ^ td.s_hdr) * 1099511628211ull;
+                    h = (h ^ td.s_len) * 1099511628211ull;
+                    const uint32_t *w = stream.data() + td.s_begin;
+                    for (uint32_t k = 0; k < td.s_len; ++k) h = (h ^ w[k]) * 1099511628211ull;
+                    key[(size_t)t] = h;
+                }
+            });
+            std::vector<int32_t> by_key(nt);
+            for (size_t t = 0; t < nt; ++t) by_key[t] = (int32_t)t;
+            std::sort(by_key.begin(), by_key.end(), [&](int32_t a, int32_t b) { return key[(size_t)a] != key[(size_t)b] ? key[(size_t)a] < key[(size_t)b] : a < b; });
+            auto same = [&](int32_t a, int32_t b) {      // the hash only proposes: the bytes decide
+                const sbk::TileDesc &x = tiles[(size_t)a], &y = tiles[(size_t)b];
+                return x.s_hdr == y.s_hdr && x.s_len == y.s_len &&
+                       std::memcmp(stream.data() + x.s_begin, stream.data() + y.s_begin, (size_t)x.s_len * 4) == 0;
+            };
+            std::vector<int32_t> rep(nt), uses(nt, 0);      // rep[t] = the first tile (in tile order) with t's program
+            std::vector<int32_t> reps;
+            for (size_t g0 = 0, g1; g0 < nt; g0 = g1) {
+                for (g1 = g0 + 1; g1 < nt && key[(size_t)by_key[g1]] == key[(size_t)by_key[g0]]; ++g1) {}
+                reps.clear();                               // distinct programs of this hash value (one, unless the hash collides)
+                for (size_t q = g0; q < g1; ++q) {
+                    const int32_t t = by_key[q];
+                    int32_t r = t;
+                    for (int32_t c : reps) if (same(c, t)) { r = c; break; }
+                    if (r == t) reps.push_back(t);
+                    rep[(size_t)t] = r; ++uses[(size_t)r];
+                }
+            }
+            std::vector<uint32_t> shared;
+            std::vector<uint32_t> at(nt, 0u);
+            int64_t n_programs = 0;
+            for (int pass = 0; pass < 2; ++pass)            // the shared programs first, then the tiles' own, each in tile order
+                for (size_t t = 0; t < nt; ++t)
+                    if (rep[t] == (int32_t)t && (uses[t] > 1) == (pass == 0)) {
+                        at[t] = (uint32_t)shared.size();
+                        const uint32_t *w = stream.data() + tiles[t].s_begin;
+                        shared.insert(shared.end(), w, w + tiles[t].s_len);
+                        ++n_programs;
+                    }
+            for (size_t t = 0; t < nt; ++t) tiles[t].s_begin = at[(size_t)rep[t]];
+            stream.swap(shared);
+            D.n_programs = n_programs;
+        }
         // Cost order inside a launch. Tiles of one launch share no particle, so their order is free; workgroups are dispatched
         // in index order, and a launch of a few hundred tiles puts the first 256 on a compute unit each and the rest beside
         // them. On an irregular mesh the launch lasts as long as its longest tile (40+ groups against a mean of 29): run the
@@ -596,7 +657,6 @@ void build_device(sb_solver *s) {
         }
         D.staged_particles = 0;
         for (const sbk::TileDesc &td : tiles) D.staged_particles += td.n_local;
-        D.stream_bytes = (int64_t)stream.size() * 4;
         D.tiles.upload(tiles, s->dev_bytes); D.runs_overflow.upload(overflow, s->dev_bytes);
         D.stream.upload(stream, s->dev_bytes);
         D.gather.upload(dev_gather, s->dev_bytes);

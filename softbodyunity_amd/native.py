@@ -28,7 +28,7 @@ SB_GROUP_WHOLE_MESH = 2
 # sb_tuning.flags (include/softbody_debug.h): A/B measurement switches, same bits for every setting
 (SB_TUNE_NO_MASS_PALETTE, SB_TUNE_NO_UNIFORM_MASS, SB_TUNE_NO_PALETTE, SB_TUNE_NO_WAVE_ITEMS, SB_TUNE_NO_LANE_PACK, SB_TUNE_NO_COST_ORDER,
  SB_TUNE_NO_FUSED_UNPACK, SB_TUNE_PEER_COARSE, SB_TUNE_NO_LAZY_TICK, SB_TUNE_NO_PACK, SB_TUNE_NO_PEEK, SB_TUNE_NO_KIN_FUSE,
- SB_TUNE_NO_WIDE_SLOTS, SB_TUNE_AUTO_PREFER_OVERLAP, SB_TUNE_NO_AUTO_CALIBRATION) = (1 << k for k in range(15))
+ SB_TUNE_NO_WIDE_SLOTS, SB_TUNE_AUTO_PREFER_OVERLAP, SB_TUNE_NO_AUTO_CALIBRATION, SB_TUNE_NO_SHARED_PROGRAMS) = (1 << k for k in range(16))
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -272,7 +272,7 @@ _TUNE_FLAG_ENV = (("SB_NO_MASS_PALETTE", SB_TUNE_NO_MASS_PALETTE), ("SB_NO_UNIFO
                   ("SB_NO_FUSED_UNPACK", SB_TUNE_NO_FUSED_UNPACK), ("SB_PEER_COARSE", SB_TUNE_PEER_COARSE), ("SB_NO_LAZY_TICK", SB_TUNE_NO_LAZY_TICK),
                   ("SB_NO_PACK", SB_TUNE_NO_PACK), ("SB_NO_PEEK", SB_TUNE_NO_PEEK), ("SB_NO_KIN_FUSE", SB_TUNE_NO_KIN_FUSE),
                   ("SB_NO_WIDE_SLOTS", SB_TUNE_NO_WIDE_SLOTS), ("SB_AUTO_PREFER_OVERLAP", SB_TUNE_AUTO_PREFER_OVERLAP),
-                  ("SB_NO_AUTO_CALIBRATION", SB_TUNE_NO_AUTO_CALIBRATION))
+                  ("SB_NO_AUTO_CALIBRATION", SB_TUNE_NO_AUTO_CALIBRATION), ("SB_NO_SHARED_PROGRAMS", SB_TUNE_NO_SHARED_PROGRAMS))
 _TUNE_INT_ENV = (("SB_TILE_LANES", "tile_lanes"), ("SB_QUAD_LANES", "quad_lanes"), ("SB_NARROW_MIN_TILES", "narrow_min_tiles"),
                  ("SB_STORE_THROUGH_MAX_TILES", "store_through_max_tiles"), ("SB_STORE_THROUGH_LARGE", "store_through_large"),
                  ("SB_PEEK_MIN_TILES", "peek_min_tiles"), ("SB_LDS_PAD", "lds_pad_bytes"), ("SB_WIN_DWORDS", "win_dwords"),
