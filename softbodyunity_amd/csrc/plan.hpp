@@ -47,7 +47,7 @@ struct Grid {
     float ext[3] = {0, 0, 0};
 };
 // cells of margin around a rank's block that its window must cover: the T1 tiles it runs reach less than one cell beyond the
-// block, and the labels of the static split inside them depend on constraints less than one further cell away (plan.cpp)
+// block, and the labels of the static split inside them depend on constraints less than one further cell away (plan.cpp propagate_labels)
 constexpr int kWindowMarginCells = 2;
 
 struct Opts {
@@ -76,7 +76,7 @@ constexpr int kMaxTileLocal = 1024;         // particles staged per tile (4 per 
 constexpr int kMaxTileRuns = 64;
 constexpr int64_t kMergedTileCap = 512;     // particles (of the grid cells) a merged tile of a balanced list may hold: stays a small tile
 constexpr int kMaxMergedCells = 8;           // ... and of how many original tiles (grid cells) it may be the union
-constexpr int kMaxBalancedLists = 3;        // of the T2 layers, at most this many are balanced lists (plan.cpp static split)
+constexpr int kMaxBalancedLists = 3;        // of the T2 layers, at most this many are balanced lists (plan.cpp balance_lists)
 constexpr int kMaxT2Layers = 6;             // shifted grids tried in turn for the constraints inside neither T0 nor T1
 // partition cost units: a particle 12; a constraint 12 / 24 / 48 (distance / volume / bending), split evenly over its vertices
 constexpr int64_t kCostParticle = 12;

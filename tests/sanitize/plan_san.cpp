@@ -11,50 +11,14 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "plan_meshes.hpp"
 
 namespace {
 
-struct Mesh {
-    std::vector<float> rest;
-    std::vector<int32_t> dist, vol, bend;
-};
-
-Mesh lattice(int n) {
-    Mesh m;
-    for (int z = 0; z < n; ++z) for (int y = 0; y < n; ++y) for (int x = 0; x < n; ++x) { m.rest.push_back((float)x); m.rest.push_back((float)y); m.rest.push_back((float)z); }
-    auto id = [n](int x, int y, int z) { return (z * n + y) * n + x; };
-    for (int z = 0; z < n; ++z) for (int y = 0; y < n; ++y) for (int x = 0; x < n; ++x) {
-        if (x + 1 < n) { m.dist.push_back(id(x, y, z)); m.dist.push_back(id(x + 1, y, z)); }
-        if (y + 1 < n) { m.dist.push_back(id(x, y, z)); m.dist.push_back(id(x, y + 1, z)); }
-        if (z + 1 < n) { m.dist.push_back(id(x, y, z)); m.dist.push_back(id(x, y, z + 1)); }
-    }
-    return m;
-}
-
-Mesh cloud(int n, unsigned seed) {     // jittered points, each joined to a few near neighbours by index proximity
-    Mesh m;
-    std::mt19937 rng(seed);
-    std::uniform_real_distribution<float> u(0.0f, 1.0f);
-    const int side = (int)std::ceil(std::cbrt((double)n));
-    for (int p = 0; p < n; ++p) {
-        int x = p % side, y = (p / side) % side, z = p / (side * side);
-        m.rest.push_back(x + 0.6f * u(rng)); m.rest.push_back(y + 0.6f * u(rng)); m.rest.push_back(z + 0.6f * u(rng));
-    }
-    auto ok = [n](int q) { return q >= 0 && q < n; };
-    for (int p = 0; p < n; ++p) {
-        const int nb[5] = {p + 1, p + side, p + side * side, p + side + 1, p - side + 1};
-        for (int q : nb) if (ok(q) && q != p) { m.dist.push_back(p); m.dist.push_back(q); }
-        if (ok(p + 1) && ok(p + side) && ok(p + side * side)) {
-            m.vol.push_back(p); m.vol.push_back(p + 1); m.vol.push_back(p + side); m.vol.push_back(p + side * side);
-            if (p % 3 == 0) { m.bend.push_back(p); m.bend.push_back(p + 1); m.bend.push_back(p + side); m.bend.push_back(p + side * side); }
-        }
-    }
-    return m;
-}
+using namespace meshes;
 
 void check(const Mesh &m, int world, int tile, int partition = 0) {
-    sbp::Input in{m.rest.data(), (int32_t)(m.rest.size() / 3), m.dist.data(), (int64_t)m.dist.size() / 2,
-                  m.vol.data(), (int64_t)m.vol.size() / 4, m.bend.data(), (int64_t)m.bend.size() / 4};
+    const sbp::Input in = m.input();
     for (int rank = 0; rank < world; rank += (world > 4 ? 3 : 1)) {
         sbp::Opts o; o.rank = rank; o.world = world; o.tile_particles = tile; o.partition = partition;
         sbp::Plan P; sbp::LocalPlan L;
@@ -71,31 +35,6 @@ void check(const Mesh &m, int world, int tile, int partition = 0) {
     }
 }
 
-// An L-shaped part of the cloud (three quarters of the box empty in one corner region): fill < 0.8, so the fill-aware grid, the
-// balanced extra lists and the tile merge of plan.cpp run; automatic partition => RCB.
-Mesh l_shape(const Mesh &full) {
-    const int32_t n = (int32_t)(full.rest.size() / 3);
-    float hi[3] = {0, 0, 0};
-    for (int32_t p = 0; p < n; ++p) for (int a = 0; a < 3; ++a) hi[a] = std::max(hi[a], full.rest[3 * p + a]);
-    std::vector<int32_t> map((size_t)n, -1);
-    Mesh m;
-    for (int32_t p = 0; p < n; ++p) {
-        const float *x = &full.rest[3 * (size_t)p];
-        if (x[0] > 0.45f * hi[0] && x[1] > 0.45f * hi[1]) continue;         // cut a column out
-        map[(size_t)p] = (int32_t)(m.rest.size() / 3);
-        m.rest.insert(m.rest.end(), x, x + 3);
-    }
-    auto keep = [&](const std::vector<int32_t> &src, int nv, std::vector<int32_t> &dst) {
-        for (size_t k = 0; k + nv <= src.size(); k += nv) {
-            bool ok = true;
-            for (int a = 0; a < nv; ++a) ok &= map[(size_t)src[k + a]] >= 0;
-            if (ok) for (int a = 0; a < nv; ++a) dst.push_back(map[(size_t)src[k + a]]);
-        }
-    };
-    keep(full.dist, 2, m.dist); keep(full.vol, 4, m.vol); keep(full.bend, 4, m.bend);
-    return m;
-}
-
 // Sharded authoring: every rank plans the window rank_window() gives it; owned counts must add up to the whole mesh and the pair
 // hashes must be symmetric.
 void check_sharded(const Mesh &m, int world, int tile) {
@@ -107,21 +46,8 @@ void check_sharded(const Mesh &m, int world, int tile) {
     int64_t owned_total = 0;
     for (int rank = 0; rank < world; ++rank) {
         sbp::Opts o; o.rank = rank; o.world = world; o.tile_particles = tile; o.domain = dom; o.partition = 1;
-        int clo[3], chi[3]; double blo[3], bhi[3];
-        sbp::rank_window(dom, o, clo, chi, blo, bhi);
-        std::vector<int32_t> gid, map((size_t)whole.n, -1);
-        Mesh w;
-        for (int32_t p = 0; p < whole.n; ++p) {
-            bool in = true;
-            for (int a = 0; a < 3; ++a) in &= m.rest[3 * (size_t)p + a] >= blo[a] && m.rest[3 * (size_t)p + a] < bhi[a];
-            if (!in) continue;
-            map[(size_t)p] = (int32_t)gid.size(); gid.push_back(p);
-            w.rest.insert(w.rest.end(), &m.rest[3 * (size_t)p], &m.rest[3 * (size_t)p] + 3);
-        }
-        for (size_t k = 0; k + 2 <= m.dist.size(); k += 2)
-            if (map[(size_t)m.dist[k]] >= 0 && map[(size_t)m.dist[k + 1]] >= 0) { w.dist.push_back(map[(size_t)m.dist[k]]); w.dist.push_back(map[(size_t)m.dist[k + 1]]); }
-        sbp::Input in{w.rest.data(), (int32_t)gid.size(), w.dist.data(), (int64_t)w.dist.size() / 2, nullptr, 0, nullptr, 0};
-        in.global_id = gid.data();
+        const Mesh w = cut_window(m, dom, o);
+        const sbp::Input in = w.input();
         sbp::Plan P; sbp::LocalPlan L;
         sbp::build_plan(in, o, P);
         sbp::extract_local(P, in, rank, L);
