@@ -40,7 +40,7 @@ constexpr int kInlineRuns = 10;
 // each of its (at most three) rounds and keeps them in registers for both passes; the slots need 9 + 9 bits of tile-local indices and a
 // palette index. Stored as ONE 16-byte word per lane -- six 21-bit fields {i:9 | j:9 | palette:3}, field 2 r + u = the lane's slot u of
 // round r (constraint lane + 128 u of that round; beyond the round's count the field is 0) -- the tile's data is 2 KiB instead of 3 KiB
-// (4 bytes per slot), it arrives in the lane's first window load and never touches LDS. build_device decides per tile (solver.hip).
+// (4 bytes per slot), it arrives in the lane's first window load and never touches LDS. The host decides per tile (tables_host.cpp pack_form).
 // A tile whose slots are NOT dictionary-coded (per-spring rest lengths) packs the same way with its rest values behind the index words:
 // [128 x 16 B index word][128 x 16 B: rest of fields 0..3][128 x 8 B: rest of fields 4, 5] = 40 bytes per lane instead of 48
 // (n_pal == 0 marks this form; only in the kernels that read inverse masses as floats, WPAL = false -- the host packs accordingly).
@@ -55,7 +55,7 @@ constexpr uint32_t kWidePackDwords = 2 * kWidePackLanes;
 constexpr int kWide8MaxTiles = 768;     // launches of at most this many spring-only small tiles run 512-lane workgroups (schedule.hip launch_tile)
 // Register-resident programs (tile_kernel): a tile of at most this many distance rounds keeps its slots and rest lengths in registers.
 // Build switches of A/B timing variants (make EXTRA=-D...): the HOST reads the same constants when it decides which tiles to lane-pack
-// (tables.hip) -- a lane-packed tile is never staged in LDS, so only the register-resident path can decode it.
+// (tables_host.cpp) -- a lane-packed tile is never staged in LDS, so only the register-resident path can decode it.
 #ifndef SB_REG_ROUNDS
 #define SB_REG_ROUNDS 4          // 256-lane workgroups (one constraint per lane and round)
 #endif
@@ -131,7 +131,7 @@ constexpr int kHaloNone = 0, kHaloGhosts = 1;
 // so a lane projects kRoundSlots / THREADS of them per round. Fewer waves per tile = more tiles resident per CU (the
 // wave slots, not LDS, cap a 256-lane workgroup at 8 tiles per CU; 128 lanes reach the 12-14 that LDS allows): +4.4 %
 // at 256^3. A launch whose tiles all fit on the chip at once is latency-bound instead and wants the wide workgroup
-// (64^3: 256 lanes are 22 % faster), so the host picks per launch (solver.hip launch_tile).
+// (64^3: 256 lanes are 22 % faster), so the host picks per launch (schedule.hip launch_tile).
 constexpr int kNarrowTileThreads = 128;                     // small tiles, launches that oversubscribe the chip
 constexpr int kQuadTileThreads = 512;                       // tiles with four-lane constraints (tets, hinges): 8 wave slots per group row
 constexpr int kWideTileThreads = 256;                       // small tiles in latency-bound launches, and all large tiles
@@ -142,7 +142,7 @@ typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));     // native vectors: one 16-byte load/store, no struct copies
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// ---- peer-store halo transport (opt-in, SB_HALO_TRANSPORT=peer; solver.hip) ---------------------------------------
+// ---- peer-store halo transport (opt-in, SB_HALO_TRANSPORT=peer; schedule.hip) ---------------------------------------
 // Instead of pack -> ncclSend/ncclRecv -> unpack, the push kernel stores every peer's ghosts STRAIGHT into that peer's
 // mailbox (one fine-grained device allocation per rank, mapped into the senders by IPC handle or, inside one process, by
 // plain pointer) and raises a flag there; its last workgroup then waits until the flags of this rank's own senders have

@@ -2,7 +2,7 @@
 // buffers, the solver object. Nothing declared here is exported (exports.map keeps the dynamic symbol table to sb_*).
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
-// Units: binding.hip (errors, RCCL / HIP runtime binding), tables.hip (plan -> device tables), schedule.hip (launches, ghost exchange, the
+// Units: binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
 // tick), readback.hip (state reads / writes, render readback, kinematic targets), validate.hip (table validator), abi.hip (lifecycle,
 // authoring, finalize, stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
@@ -35,6 +35,7 @@
 #include "../../include/softbody_group.h"
 #include "kernel_types.hpp"
 #include "plan.hpp"
+#include "tables_host.hpp"
 
 namespace sbi {
 
@@ -114,23 +115,10 @@ struct DevHalo {                 // one halo slot: who we talk to and which part
     bool active() const { return !peers.empty(); }
 };
 
-struct DevTiling {
-    int32_t n_tiles = 0;
-    size_t lds_bytes = 0;
-    int64_t n_slots = 0;         // constraints stored in the tile streams
-    int64_t staged_particles = 0;   // sum of n_local over the device tiles
-    int64_t stream_bytes = 0;    // bytes of the tile streams (round words, palettes, slots) the tiles read: sum of s_len x 4, shared programs counted per tile
-    int64_t n_programs = 0;      // distinct programs held in `stream` (tiles with identical programs share one copy; stream.count x 4 = bytes uploaded)
-    int32_t max_local = 0, win_dwords = 4, pal_dwords = 0, rounds_dwords = 0;
-    int32_t n_boundary = 0;      // world > 1: T0 -- the FIRST n_boundary tiles hold every particle some peer needs; T1 -- the LAST
-                                 // n_boundary tiles hold every ghost and every sent particle
-    bool has_quads = false;
-    int32_t item_waves = 0;      // waves per tile the wave items were dealt for (0 = the streams hold none)
-    int32_t packed_lanes = 0;    // 128: tiles of this tiling may hold lane-packed slots (kernels.hip.hpp kLanePack*): EVERY launch of it runs 128-lane workgroups
-    int64_t n_packed_tiles = 0;
+struct DevTiling : sbt::TilingScalars {
     DevBuf<sbk::TileDesc> tiles;
     DevBuf<int2> runs_overflow;
-    DevBuf<uint32_t> stream;     // per tile: [round words][rest-length dictionary][round data], see kernels.hip.hpp
+    DevBuf<uint32_t> stream;     // per tile: [round words][rest-length dictionary][round data], see kernel_types.hpp
     DevBuf<int32_t> gather;      // T2: particle lists of the tiles (local numbering)
 };
 
@@ -260,7 +248,7 @@ struct sb_solver {
     bool group_walk = false;         // a rank of a group whose host thread walks the tick across the ranks (group.hip): exchanges are issued there
     bool capturing = false;          // sb_step is recording the tick into a hipGraph right now
     sbi::ExchangeTimer xtimer;       // sb_debug_exchange_timing
-    // peer-store halo transport (SB_HALO_TRANSPORT=peer; kernels.hip.hpp): one mailbox per rank = [header words | ghost segments]
+    // peer-store halo transport (SB_HALO_TRANSPORT=peer; aux_kernels.hip.hpp): one mailbox per rank = [header words | ghost segments]
     struct PeerState {
         bool enabled = false, linked = false, fine_grained = false;
         uint32_t *mailbox = nullptr;            // header: words 0-1 = the rank's plan hash, 2 = sharded?, 4 .. 4+2W = its pair hashes; per slot: data flags[world], ack flags[world], epoch, 2 counters; then the offset table
@@ -272,7 +260,7 @@ struct sb_solver {
         std::vector<sbk::PeerSlot> slots;
         uint32_t *local = nullptr;              // 8 ordinary (cached) words per slot: epoch, workgroup counters, go words
         uint32_t *h_error = nullptr;            // pinned host word the kernels set when a wait gives up: the host reads it without a copy
-        size_t slot_base(int slot, int world) const { return 4 + 2 * (size_t)world + (size_t)slot * (2 * (size_t)world + 3); }
+        size_t slot_base(int slot, int world) const { return sbt::mailbox_slot_base(slot, world); }
     } peer;
     // asynchronous render readback (sb_readback_begin / sb_readback_end): two snapshot slots
     hipStream_t copy_stream = nullptr;
@@ -376,7 +364,7 @@ struct sb_solver {
 
 namespace sbi {
 
-// ---- tables.hip: plan -> device tables ---------------------------------------------------------------------------------------------
+// ---- tables.hip: plan -> device tables (built by tables_host.cpp) ---------------------------------------------------------------------------------------------
 sbp::Input make_input(const float *rest, int32_t n, const int32_t *d, int64_t md, const int32_t *v, int64_t mv, const int32_t *b, int64_t mb);
 sbp::Domain to_domain(const sb_domain &d);
 // The planner options behind the ABI's fields: ONE rule for sb_finalize and sb_plan_build

@@ -6,7 +6,7 @@
 
 namespace sbk {
 
-// One workgroup = one tile (or one pack of under-full tiles, solver.hip build_device) of THREADS lanes; a tile owns one
+// One workgroup = one tile (or one pack of under-full tiles, tables_host.cpp pack_tiles) of THREADS lanes; a tile owns one
 // constraint list, cut into rounds of at most kRoundSlots independent constraints (plan.hpp):
 //   KIND 0 (first kernel of a tick)  : MARK: v from the velocity array, integrate; the tile's rounds
 //   KIND 1 (every other substep)     : the tile's rounds (finish substep s-1), MARK: v = (x-xprev)/h, integrate
@@ -17,7 +17,7 @@ namespace sbk {
 //                                      ended and the integrate of the next one a particle with w = 0 that has a target takes it
 //   KIND 4 (peek at the tick's end)   : what KIND 2 would leave as positions (the tile's rounds + collide), written to a side
 //                                      array; nothing of the state is written, so the deferred last kernel of a tick can still
-//                                      be fused with the first kernel of the next one (render readback, solver.hip peek_positions)
+//                                      be fused with the first kernel of the next one (render readback, schedule.hip peek_positions)
 // Particles AND the tile's constraint stream are staged in LDS with wide coalesced loads issued together,
 // so a tile pays the HBM latency once; rounds then run LDS-to-LDS with one barrier each. Each lane keeps
 // ownership of up to PPT particles for the MARK step and projects kRoundSlots / THREADS constraints per round.

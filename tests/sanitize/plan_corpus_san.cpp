@@ -2,7 +2,7 @@
 // generator: particles on a point, a line, a plane, chains, complete graphs, hubs, isolated particles, no constraints, one or two particles,
 // duplicate constraints, extreme scales, NaN / infinite positions; world up to 17, tile sizes down to 1, every partition -- and from
 // tests/fuzz/fuzz_windows.py's: ranks' WINDOWS of lattice boxes with their domain and whole-mesh ids, sharded authoring). Each entry is
-// planned for every rank; an exception is a refusal (counted), anything the sanitizers see is a failure. CPU only.
+// planned for every rank and its tables are built (tables_san.hpp); an exception of the planner is a refusal (counted), one of the table builder and anything the sanitizers see is a failure. CPU only.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -10,12 +10,13 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "tables_san.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: plan_corpus_san <corpus>\n"); return 2; }
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) { std::perror("corpus"); return 2; }
-    int planned = 0, refused = 0, entries = 0;
+    int planned = 0, refused = 0, entries = 0, tabled = 0;
     for (;;) {
         int32_t h[12];
         if (std::fread(h, sizeof(int32_t), 12, f) != 12) break;
@@ -47,16 +48,23 @@ int main(int argc, char **argv) {
             }
             // (the ABI resolves the automatic tile size before it calls the planner: 0 -> 512, or 256 with 4-vertex constraints)
             if (o.tile_particles == 0) o.tile_particles = (mv + mb > 0) ? 256 : 512;
+            sbp::Plan P; sbp::LocalPlan L;
             try {
-                sbp::Plan P; sbp::LocalPlan L;
                 sbp::build_plan(in, o, P);
                 sbp::extract_local(P, in, rank, L);
                 if ((int64_t)P.order_id[0].size() != (int64_t)md + mv + mb) { std::fprintf(stderr, "entry %d: order does not cover every constraint\n", entries); return 1; }
                 ++planned;
-            } catch (const std::exception &) { ++refused; }
+            } catch (const std::exception &) { ++refused; continue; }
+            // the tables of a plan the planner accepted: nothing in this corpus comes near the one refusal the builder has (a stream of
+            // 2^32 dwords), so an exception here -- an "internal:" error, a failed invariant of tables_san.hpp -- is a failure
+            try {
+                san_tables(in, P, L);
+                ++tabled;
+            } catch (const std::exception &e) { std::fprintf(stderr, "entry %d rank %d: table builder: %s\n", entries, rank, e.what()); return 1; }
         }
     }
     std::fclose(f);
+    if (tabled != planned) { std::fprintf(stderr, "tables built for %d of %d plans\n", tabled, planned); return 1; }
     std::printf("SANITIZE OK entries %d plans %d refused %d\n", entries, planned, refused);
     return 0;
 }

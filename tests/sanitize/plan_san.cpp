@@ -1,4 +1,5 @@
-// AddressSanitizer / UBSan driver for the host planner (softbodyunity_amd/csrc/plan.cpp): builds plans for a lattice, an
+// AddressSanitizer / UBSan driver for the host planner and the host table builder (softbodyunity_amd/csrc/plan.cpp, tables_host.cpp):
+// builds plans, and the tables of every plan (tables_san.hpp), for a lattice, an
 // irregular cloud with 4-vertex constraints and a few degenerate inputs, for several world sizes, and checks the basic
 // partition invariants. CPU only (GPU sanitizers are not available on the pool); built and run by tests/test_sanitizers.py.
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include "plan.hpp"
 #include "plan_meshes.hpp"
+#include "tables_san.hpp"
 
 namespace {
 
@@ -32,6 +34,7 @@ void check(const Mesh &m, int world, int tile, int partition = 0) {
         if (L.n_owned < 0 || L.n_owned > (int64_t)L.local_to_old.size()) throw std::runtime_error("bad owned count");
         for (const auto &H : L.halo)
             if ((int)H.send_idx.size() != world || (int)H.recv_idx.size() != world) throw std::runtime_error("halo slot size");
+        san_tables(in, P, L);
     }
 }
 
@@ -51,6 +54,7 @@ void check_sharded(const Mesh &m, int world, int tile) {
         sbp::Plan P; sbp::LocalPlan L;
         sbp::build_plan(in, o, P);
         sbp::extract_local(P, in, rank, L);
+        san_tables(in, P, L);
         owned_total += L.n_owned;
         pair[(size_t)rank] = L.pair_hash;
     }
