@@ -55,6 +55,8 @@ namespace SoftbodyMI355X
         [SerializeField] bool asyncReadback = false;
         [Tooltip("With asyncReadback: copy only the particles the render triangles use (a volumetric body renders its surface only); the MeshFilter's mesh is rebuilt over that set.")]
         [SerializeField] bool renderSetOnly = false;
+        [Tooltip("With asyncReadback on a tet cage (volumeIJKL): a separate, finer visual mesh. It is bound to the cage at Start (SoftbodyMeshBuilder.EmbedVertices) and skinned on the GPU every tick (SPEC.md 6b); the MeshFilter then shows it instead of the particles.")]
+        [SerializeField] Mesh visualMesh = null;
 
         // constraint graph (filled by an authoring script or SoftbodyMeshBuilder before Start)
         public Vector3[] restPositions;
@@ -140,7 +142,20 @@ namespace SoftbodyMI355X
                 SoftbodyNative.Check(SoftbodyNative.sb_group_set_ground_plane(handle, groundNormal.x, groundNormal.y, groundNormal.z, groundOffset, 1), "sb_group_set_ground_plane");
             SoftbodyNative.Check(SoftbodyNative.sb_group_finalize(handle), "sb_group_finalize");
             posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
-            if (asyncReadback && renderTriangles != null && renderTriangles.Length >= 3)
+            if (asyncReadback && visualMesh != null && volumeIJKL != null && volumeIJKL.Length >= 4)
+            {
+                // embedded render mesh: bind every visual vertex to the tet that holds it in the rest pose, hand cage + weights + the visual
+                // triangles over once; from here on a readback delivers the skinned visual vertices and their normals (no particle leaves the GPU)
+                Vector3[] visual = visualMesh.vertices;
+                int[] visualTri = visualMesh.triangles;
+                SoftbodyMeshBuilder.EmbedVertices(restPositions ?? positions, volumeIJKL, visual, out int[] cage, out float[] weights);
+                SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_embedding(handle, cage, weights, visual.Length, visualTri, visualTri.Length / 3), "sb_group_set_render_embedding");
+                posPin.Free();
+                positions = (Vector3[])visual.Clone(); normals = new Vector3[visual.Length];      // (what FixedUpdate copies the snapshot into)
+                posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
+                mesh.Clear(); mesh.vertices = positions; mesh.triangles = visualTri; mesh.uv = visualMesh.uv;
+            }
+            else if (asyncReadback && renderTriangles != null && renderTriangles.Length >= 3)
             {
                 SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_triangles(handle, renderTriangles, renderTriangles.Length / 3), "sb_group_set_render_triangles");
                 normals = new Vector3[positions.Length];

@@ -1,5 +1,5 @@
 // SoftbodyMeshBuilder.cs — Unity Mesh -> particles + constraint graph for the Softbody component
-// (SURVEY.md §8f item 2). C# twin of softbodyunity_amd/mesh.py::from_triangle_mesh / from_tet_mesh, which is
+// (SURVEY.md §8f item 2). C# twin of softbodyunity_amd/mesh.py::from_triangle_mesh / from_tet_mesh / embed_vertices, which is
 // what the test-suite runs (tests/test_authoring.py): no C# toolchain exists in the build image. The reference
 // repository has no authoring code to mirror (/root/reference/README.md:1 is its only line).
 using System;
@@ -79,6 +79,77 @@ namespace SoftbodyMI355X
             sb.restPositions = (Vector3[])nodes.Clone(); sb.positions = (Vector3[])nodes.Clone();
             sb.distanceIJ = ij.ToArray(); sb.distanceRest = rest.ToArray();
             sb.volumeIJKL = idx.ToArray(); sb.volumeRest = vol.ToArray();
+        }
+
+        /// Bind a visual mesh to a tet cage (SPEC.md 6b; twin of softbodyunity_amd/mesh.py embed_vertices): per vertex the tet that holds it in
+        /// the rest pose (cage: its 4 corners in the tet's order) and the vertex' barycentric coordinates in it (weights), computed in double
+        /// and cast at the end. A vertex inside no tet takes the tet whose smallest coordinate is largest: it extrapolates, some weights are
+        /// negative. The tets searched for a vertex are those incident to its nearest cage nodes (a hash grid over the nodes), nearest first.
+        public static void EmbedVertices(Vector3[] nodes, int[] tets, Vector3[] vertices, out int[] cage, out float[] weights)
+        {
+            int nt = tets.Length / 4;
+            var incident = new List<int>[nodes.Length];
+            double edgeSum = 0;
+            for (int t = 0; t < nt; ++t)
+            {
+                for (int q = 0; q < 4; ++q) { int p = tets[4 * t + q]; if (incident[p] == null) incident[p] = new List<int>(); incident[p].Add(t); }
+                edgeSum += (nodes[tets[4 * t + 1]] - nodes[tets[4 * t]]).magnitude;
+            }
+            double cell = Math.Max(edgeSum / Math.Max(nt, 1), 1e-9);
+            var grid = new Dictionary<(long, long, long), List<int>>();
+            Func<Vector3, (long, long, long)> keyOf = v => ((long)Math.Floor(v.x / cell), (long)Math.Floor(v.y / cell), (long)Math.Floor(v.z / cell));
+            for (int p = 0; p < nodes.Length; ++p)
+            {
+                if (incident[p] == null) continue;             // a node no tet uses cannot lead to one
+                var k = keyOf(nodes[p]);
+                if (!grid.TryGetValue(k, out var l)) { l = new List<int>(); grid[k] = l; }
+                l.Add(p);
+            }
+            cage = new int[4 * vertices.Length]; weights = new float[4 * vertices.Length];
+            var near = new List<int>();
+            var lam = new double[4]; var best = new double[4];
+            for (int v = 0; v < vertices.Length; ++v)
+            {
+                // the nodes of the smallest cube of grid cells around the vertex that holds at least 12 (or every node), nearest first
+                var c = keyOf(vertices[v]);
+                near.Clear();
+                for (long ring = 1; near.Count < Math.Min(12, nodes.Length) && ring < (1L << 20); ring *= 2)
+                {
+                    near.Clear();
+                    for (long dz = -ring; dz <= ring; ++dz) for (long dy = -ring; dy <= ring; ++dy) for (long dx = -ring; dx <= ring; ++dx)
+                        if (grid.TryGetValue((c.Item1 + dx, c.Item2 + dy, c.Item3 + dz), out var l)) near.AddRange(l);
+                    if (near.Count >= grid.Count && ring > 1) break;
+                }
+                Vector3 x = vertices[v];
+                near.Sort((a, b) => (nodes[a] - x).sqrMagnitude.CompareTo((nodes[b] - x).sqrMagnitude));
+                double bestMin = double.NegativeInfinity; int bestTet = -1;
+                for (int j = 0; j < Math.Min(12, near.Count) && bestMin < -1e-12; ++j)
+                    foreach (int t in incident[near[j]])
+                    {
+                        if (!Barycentric(nodes, tets, t, x, lam)) continue;
+                        double mn = Math.Min(Math.Min(lam[0], lam[1]), Math.Min(lam[2], lam[3]));
+                        if (mn > bestMin) { bestMin = mn; bestTet = t; Array.Copy(lam, best, 4); }
+                    }
+                if (bestTet < 0) throw new ArgumentException("EmbedVertices: no tet found for a vertex (empty or degenerate cage?)");
+                for (int q = 0; q < 4; ++q) { cage[4 * v + q] = tets[4 * bestTet + q]; weights[4 * v + q] = (float)best[q]; }
+            }
+        }
+
+        // lam = barycentric coordinates of x in tet t (Cramer's rule in double); false for a degenerate tet
+        static bool Barycentric(Vector3[] nodes, int[] tets, int t, Vector3 x, double[] lam)
+        {
+            Vector3 p0 = nodes[tets[4 * t]];
+            double[] a = D(nodes[tets[4 * t + 1]], p0), b = D(nodes[tets[4 * t + 2]], p0), c = D(nodes[tets[4 * t + 3]], p0), r = D(x, p0);
+            double det = Det(a, b, c);
+            if (det == 0.0) return false;
+            lam[1] = Det(r, b, c) / det; lam[2] = Det(a, r, c) / det; lam[3] = Det(a, b, r) / det;
+            lam[0] = 1.0 - lam[1] - lam[2] - lam[3];
+            return true;
+        }
+        static double[] D(Vector3 p, Vector3 q) { return new[] { (double)p.x - q.x, (double)p.y - q.y, (double)p.z - q.z }; }
+        static double Det(double[] a, double[] b, double[] c)
+        {
+            return a[0] * (b[1] * c[2] - b[2] * c[1]) - a[1] * (b[0] * c[2] - b[2] * c[0]) + a[2] * (b[0] * c[1] - b[1] * c[0]);
         }
 
         /// Gmsh .msh, ASCII 2.2 or 4.1: the 4-node tetrahedra (element type 4) of the file -> FromTetMesh. Node tags need not be

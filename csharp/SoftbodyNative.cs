@@ -157,6 +157,8 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_begin(IntPtr s);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_end(IntPtr s, out IntPtr posXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_triangles(IntPtr s, int[] triAbc, int m);
+        // embedded render vertices (SPEC.md 6b): cageIjkl 4 particle indices and weights4 4 floats per render vertex, triAbc over RENDER VERTICES (may be null with mTri = 0)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_embedding(IntPtr s, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_normals(IntPtr s, out IntPtr normalXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_render_set_only(IntPtr s, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_render_set(IntPtr s, out IntPtr ids, out int count);
@@ -210,6 +212,7 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_state(IntPtr g, IntPtr posXyz, IntPtr velXyz, int n);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_kinematic_positions(IntPtr g, IntPtr ids, IntPtr posXyz, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_triangles(IntPtr g, int[] triAbc, int m);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_embedding(IntPtr g, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_readback_render_set_only(IntPtr g, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_begin(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_end(IntPtr g, out IntPtr posXyz);

@@ -218,6 +218,22 @@ int sb_readback_get_normals(sb_solver *s, const float **normal_xyz_out);
  * world > 1: the render particles THIS RANK owns, ids ascending in its numbering. Not while a readback is pending. */
 int sb_set_readback_render_set_only(sb_solver *s, int32_t render_set_only);
 int sb_readback_get_render_set(sb_solver *s, const int32_t **ids_out, int32_t *count_out);
+/* Embedded render vertices (SPEC.md 6b): the usual way a soft body ships -- a coarse simulated cage (tet mesh, lattice) and a finer visual
+ * mesh bound to it. Render vertex r is bound to four particles cage_ijkl[4r .. 4r+3] (caller numbering; any four, repeats allowed; normally
+ * the corners of the tet that holds it in the rest pose) with four weights weights4[4r .. 4r+3], used as given (not normalised; negative for
+ * a vertex outside its tet): r = ((w0 x[i0] + w1 x[i1]) + w2 x[i2]) + w3 x[i3] on the tick-end positions, in binary32 without FMA. While an
+ * embedding is set, sb_readback_begin skins the visual mesh on the GPU instead of snapshotting the particles (between two ticks only the
+ * T0 tiles that hold a cage particle are peeked), the pointer of sb_readback_end addresses m_vertices*3 floats in the caller's vertex order,
+ * and sb_readback_get_normals m_vertices*3 floats: SPEC.md 6a on the skinned array with tri_abc, which indexes RENDER VERTICES (m_tri = 0:
+ * no normals, SB_ERR_STATE). sb_readback_get_render_set returns SB_ERR_STATE; sb_get_positions / sb_get_velocities are unchanged.
+ * The two render modes exclude each other: this call with m_vertices > 0 while render triangles are set, and sb_set_render_triangles with
+ * m > 0 while an embedding is set, return SB_ERR_STATE and change nothing -- switch the other mode off (count 0) first. Setting or clearing
+ * an embedding re-allocates its buffers and invalidates the pointers earlier readbacks of it returned. A rank of a partitioned solver
+ * (world > 1) returns SB_ERR_UNSUPPORTED: its cage particles may belong to other ranks (sb_group_set_render_embedding serves that case).
+ * m_vertices = 0 switches the embedding off. tri_abc may be NULL with m_tri = 0 (no normals). Any time after
+ * sb_set_particles, not while a readback is pending. */
+int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices,
+                            const int32_t *tri_abc, int32_t m_tri);
 int sb_get_owner(sb_solver *s, int32_t *owner_rank_out, int32_t n);
 
 

@@ -94,6 +94,12 @@ int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const floa
  * host memory. */
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri_abc, int32_t m);
 int sb_group_set_readback_render_set_only(sb_group *g, int32_t render_set_only);
+/* Embedded render vertices (sb_set_render_embedding; cage indices in the whole mesh's numbering): every rank snapshots the cage particles it
+ * owns into the gather buffer (its peek covers only the tiles that hold one), the render device skins the visual mesh from it and computes
+ * the normals of the skinned array; sb_group_readback_end / sb_group_readback_get_normals then deliver m_vertices*3 floats. Same
+ * validation, same exclusion against sb_group_set_render_triangles. */
+int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices,
+                                  const int32_t *tri_abc, int32_t m_tri);
 int sb_group_readback_begin(sb_group *g);
 int sb_group_readback_end(sb_group *g, const float **pos_xyz_out);
 int sb_group_readback_get_normals(sb_group *g, const float **normal_xyz_out);

@@ -114,9 +114,29 @@ struct sb_group {
     hipEvent_t ev_copied[kSnapSlots] = {nullptr, nullptr, nullptr};
     bool snap_compact[kSnapSlots] = {false, false, false}, snap_has_normals[kSnapSlots] = {false, false, false};
     int snap_head = 0, snap_pending = 0, snap_last_ended = -1;
+    // embedded render vertices (sb_group_set_render_embedding, SPEC.md 6b): cage in the whole mesh's numbering; excludes render_tri
+    int32_t emb_m = 0;
+    std::vector<int32_t> emb_cage, emb_tri;
+    std::vector<float> emb_w;
+    bool emb_dirty = false;
+    DevBuf<int4> d_emb_cage;
+    DevBuf<float4> d_emb_w;
+    DevBuf<int32_t> d_emb_tri, d_emb_adj_off, d_emb_adj_tri;
+    DevBuf<float> d_emb_pos[kSnapSlots], d_emb_nrm[kSnapSlots];
+    float *h_emb_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_emb_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
+    bool snap_embedded[kSnapSlots] = {false, false, false};
+    void release_embedding() {                   // on the render device; no readback is pending when the embedding changes
+        d_emb_cage.free(); d_emb_w.free(); d_emb_tri.free(); d_emb_adj_off.free(); d_emb_adj_tri.free();
+        for (int k = 0; k < kSnapSlots; ++k) {
+            d_emb_pos[k].free(); d_emb_nrm[k].free();
+            if (h_emb_pos[k]) (void)hipHostFree(h_emb_pos[k]);
+            if (h_emb_nrm[k]) (void)hipHostFree(h_emb_nrm[k]);
+            h_emb_pos[k] = h_emb_nrm[k] = nullptr;
+        }
+    }
     struct RankRender {                          // per rank, on the rank's device
         DevBuf<int32_t> d_target_of_local;       // owned particle l -> caller id (full snapshots)
-        DevBuf<int32_t> d_rs_ids, d_rs_local;    // the render particles the rank owns: caller id, device index
+        DevBuf<int32_t> d_rs_ids, d_rs_local;    // the render particles (or, with an embedding, the cage particles) the rank owns: caller id, device index
         std::vector<int32_t> rs_local;
         hipEvent_t ev_snap[kSnapSlots] = {nullptr, nullptr, nullptr};
         int64_t acct = 0;
@@ -147,6 +167,7 @@ struct sb_group {
             d_gather[k].free(); d_nrm[k].free(); d_cpos[k].free();
         }
         d_tri.free(); d_adj_off.free(); d_adj_tri.free(); d_render_set.free();
+        release_embedding();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (size_t r = 0; r < rr.size(); ++r) {
             (void)hipSetDevice(devices[r]);
@@ -641,12 +662,40 @@ int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {
     if (!g || m < 0 || (m > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: bad argument");
     if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_triangles before sb_group_set_particles");
     if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_render_triangles while a readback is pending");
+    if (m > 0 && g->emb_m > 0)
+        return fail(SB_ERR_STATE, "sb_group_set_render_triangles: a render embedding is set (switch it off first: sb_group_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
         for (int64_t c = 0; c < 3 * (int64_t)m; ++c) if (tri[c] < 0 || tri[c] >= g->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: particle index out of range");
         g->render_tri.assign(tri, tri + 3 * (size_t)m);
         g->render_dirty = true;
         if (m == 0) g->render_set_only = false;
         for (bool &b : g->snap_has_normals) b = false;
+        return SB_OK;
+    });
+}
+
+int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_embedding: null group");
+    if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_embedding before sb_group_set_particles");
+    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_render_embedding while a readback is pending");
+    if (m_vertices > 0 && !g->render_tri.empty())
+        return fail(SB_ERR_STATE, "sb_group_set_render_embedding: render triangles are set (switch them off first: sb_group_set_render_triangles with m = 0)");
+    return guarded([&]() -> int {
+        if (int rc = check_embedding_args("sb_group_set_render_embedding", g->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri)) return rc;
+        if (m_vertices == 0 && g->emb_m == 0) return SB_OK;      // off already
+        std::vector<int32_t> cage(cage_ijkl, cage_ijkl + 4 * (size_t)m_vertices), tri(tri_abc, tri_abc + 3 * (size_t)m_tri);
+        std::vector<float> w(weights4, weights4 + 4 * (size_t)m_vertices);
+        if (g->copy_stream) {
+            HIP_CHECK(hipSetDevice(g->device_of(0)));
+            HIP_CHECK(hipStreamSynchronize(g->copy_stream));
+            g->release_embedding();     // (pointers handed out by earlier readbacks of the embedding end here)
+        }
+        g->emb_cage.swap(cage); g->emb_w.swap(w); g->emb_tri.swap(tri);
+        g->emb_m = m_vertices;
+        g->emb_dirty = m_vertices > 0;
+        for (sb_solver *s : g->ranks) if (s) s->n_peek_tiles = -1;
+        for (bool &b : g->snap_has_normals) b = false;
+        if (g->snap_last_ended >= 0 && g->snap_embedded[g->snap_last_ended]) g->snap_last_ended = -1;
         return SB_OK;
     });
 }
@@ -716,6 +765,83 @@ int sb_group_readback_begin(sb_group *g) {
             g->render_dirty = false;
         }
         const int k = (g->snap_head + g->snap_pending) % sb_group::kSnapSlots;
+        if (g->emb_m > 0) {
+            // Embedded render vertices: every rank snapshots the cage particles it owns into the gather buffer (whole-mesh numbering),
+            // then the render device skins the visual mesh from it, computes the normals of the skinned array and copies both out.
+            const size_t m3 = (size_t)g->emb_m * 3;
+            if (g->emb_dirty) {
+                HIP_CHECK(hipStreamSynchronize(g->copy_stream));
+                g->release_embedding();
+                std::vector<int4> cage((size_t)g->emb_m);
+                std::vector<float4> w((size_t)g->emb_m);
+                std::vector<uint8_t> seen((size_t)g->n, 0);
+                std::vector<std::vector<int32_t>> ids((size_t)W), loc((size_t)W);
+                for (int32_t v = 0; v < g->emb_m; ++v) {
+                    const int32_t *c = &g->emb_cage[4 * (size_t)v];
+                    const float *ww = &g->emb_w[4 * (size_t)v];
+                    cage[(size_t)v] = make_int4(c[0], c[1], c[2], c[3]);
+                    w[(size_t)v] = make_float4(ww[0], ww[1], ww[2], ww[3]);
+                    for (int j = 0; j < 4; ++j) {
+                        if (seen[(size_t)c[j]]) continue;
+                        seen[(size_t)c[j]] = 1;
+                        const int r = g->owner[(size_t)c[j]];
+                        ids[(size_t)r].push_back(c[j]);
+                        loc[(size_t)r].push_back(local_of_old(g->ranks[(size_t)r])[(size_t)g->index_in_rank[(size_t)c[j]]]);
+                    }
+                }
+                g->d_emb_cage.upload(cage, g->dev_bytes); g->d_emb_w.upload(w, g->dev_bytes);
+                if (!g->emb_tri.empty()) {
+                    std::vector<int32_t> off, adj;
+                    build_adjacency(g->emb_tri, g->emb_m, off, adj);
+                    g->d_emb_tri.upload(g->emb_tri, g->dev_bytes); g->d_emb_adj_off.upload(off, g->dev_bytes); g->d_emb_adj_tri.upload(adj, g->dev_bytes);
+                }
+                for (int q = 0; q < sb_group::kSnapSlots; ++q) {
+                    g->d_emb_pos[q].alloc(m3, g->dev_bytes);
+                    HIP_CHECK(hipHostMalloc((void **)&g->h_emb_pos[q], m3 * sizeof(float), hipHostMallocDefault));
+                    if (!g->emb_tri.empty()) {
+                        g->d_emb_nrm[q].alloc(m3, g->dev_bytes);
+                        HIP_CHECK(hipHostMalloc((void **)&g->h_emb_nrm[q], m3 * sizeof(float), hipHostMallocDefault));
+                    }
+                }
+                for (int r = 0; r < W; ++r) {
+                    HIP_CHECK(hipSetDevice(g->device_of(r)));
+                    auto &R = g->rr[(size_t)r];
+                    R.d_rs_ids.upload(ids[(size_t)r], R.acct); R.d_rs_local.upload(loc[(size_t)r], R.acct);
+                    R.rs_local = loc[(size_t)r];
+                    g->ranks[(size_t)r]->n_peek_tiles = -1;        // the peek's tile subset follows the cage particles
+                }
+                HIP_CHECK(hipSetDevice(dev0));
+                g->emb_dirty = false;
+            }
+            float *gather = g->d_gather[k].p;
+            int rce = g->for_ranks([&](int r) {
+                return guarded([&]() -> int {
+                    sb_solver *s = g->ranks[(size_t)r];
+                    int rcd = set_device(s); if (rcd) return rcd;
+                    auto &R = g->rr[(size_t)r];
+                    const float *src = render_source(s, /*compact=*/true, R.rs_local);
+                    launch_snapshot_subset(s, src, R.d_rs_ids.p, R.d_rs_local.p, (int)R.rs_local.size(), gather);
+                    HIP_CHECK(hipEventRecord(R.ev_snap[k], s->stream));
+                    return SB_OK;
+                });
+            });
+            if (rce) return rce;
+            HIP_CHECK(hipSetDevice(dev0));
+            for (int r = 0; r < W; ++r) HIP_CHECK(hipStreamWaitEvent(g->copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
+            launch_skin(g->copy_stream, gather, g->d_emb_cage.p, g->d_emb_w.p, g->d_emb_pos[k].p, (int)g->emb_m);
+            HIP_CHECK(hipMemcpyAsync(g->h_emb_pos[k], g->d_emb_pos[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
+            g->snap_has_normals[k] = false;
+            if (!g->emb_tri.empty()) {
+                launch_normals(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->d_emb_nrm[k].p, (int)g->emb_m, nullptr, nullptr);
+                HIP_CHECK(hipMemcpyAsync(g->h_emb_nrm[k], g->d_emb_nrm[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
+                g->snap_has_normals[k] = true;
+            }
+            g->snap_compact[k] = false; g->snap_embedded[k] = true;
+            HIP_CHECK(hipEventRecord(g->ev_copied[k], g->copy_stream));
+            ++g->snap_pending;
+            return SB_OK;
+        }
+        g->snap_embedded[k] = false;
         // host buffers of this slot, by what it will carry
         if (!compact && !g->h_pos[k]) HIP_CHECK(hipHostMalloc((void **)&g->h_pos[k], n3 * sizeof(float), hipHostMallocDefault));
         if (!g->render_tri.empty()) {
@@ -779,7 +905,7 @@ int sb_group_readback_end(sb_group *g, const float **pos_xyz_out) {
         const int k = g->snap_head;
         HIP_CHECK(hipEventSynchronize(g->ev_copied[k]));
         for (sb_solver *s : g->ranks) check_peer_error(s);
-        *pos_xyz_out = g->snap_compact[k] ? g->h_cpos[k] : g->h_pos[k];
+        *pos_xyz_out = g->snap_embedded[k] ? g->h_emb_pos[k] : (g->snap_compact[k] ? g->h_cpos[k] : g->h_pos[k]);
         g->snap_last_ended = k;
         g->snap_head = (g->snap_head + 1) % sb_group::kSnapSlots; --g->snap_pending;
         return SB_OK;
@@ -790,12 +916,13 @@ int sb_group_readback_get_normals(sb_group *g, const float **out) {
     if (!g || !out) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_normals: null argument");
     if (g->snap_last_ended < 0 || !g->snap_has_normals[g->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_group_readback_get_normals: no finished readback with render triangles set");
-    *out = g->h_nrm[g->snap_last_ended];
+    *out = g->snap_embedded[g->snap_last_ended] ? g->h_emb_nrm[g->snap_last_ended] : g->h_nrm[g->snap_last_ended];
     return SB_OK;
 }
 
 int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids, int32_t *count) {
     if (!g || !ids || !count) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_render_set: null argument");
+    if (g->emb_m > 0) return fail(SB_ERR_STATE, "sb_group_readback_get_render_set: a render embedding is set (the readback brings render vertices, not particles)");
     if (g->snap_last_ended < 0 || !g->snap_has_normals[g->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_group_readback_get_render_set: no finished readback with render triangles set");
     *ids = g->render_set.data();

@@ -1,4 +1,4 @@
-// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals
+// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals and embedded render vertices
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
@@ -122,6 +122,35 @@ void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_of
     HIP_CHECK(hipGetLastError());
 }
 
+void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(sbk::skin_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src_xyz, cage, weights, out_xyz, m);
+    HIP_CHECK(hipGetLastError());
+}
+
+int check_embedding_args(const char *who, int32_t n, const int32_t *cage, const float *w, int32_t m, const int32_t *tri, int32_t m_tri) {
+    const std::string me(who);
+    if (m < 0 || m_tri < 0) return fail(SB_ERR_INVALID_ARG, me + ": negative count");
+    if ((m > 0 && (!cage || !w)) || (m_tri > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, me + ": null pointer with a positive count");
+    for (int64_t c = 0; c < 4 * (int64_t)m; ++c) {
+        if (cage[c] < 0 || cage[c] >= n) return fail(SB_ERR_INVALID_ARG, me + ": cage particle index out of range (render vertex " + std::to_string(c / 4) + ")");
+        if (!std::isfinite(w[c])) return fail(SB_ERR_INVALID_ARG, me + ": weight is NaN or infinite (render vertex " + std::to_string(c / 4) + ")");
+    }
+    for (int64_t c = 0; c < 3 * (int64_t)m_tri; ++c)
+        if (tri[c] < 0 || tri[c] >= m) return fail(SB_ERR_INVALID_ARG, me + ": triangle index out of range (triangles index render vertices)");
+    return SB_OK;
+}
+
+void build_adjacency(const std::vector<int32_t> &tri, int32_t n_vertices, std::vector<int32_t> &off, std::vector<int32_t> &adj) {
+    const int64_t m = (int64_t)tri.size() / 3;
+    off.assign((size_t)n_vertices + 1, 0); adj.resize((size_t)3 * m);
+    for (int64_t c = 0; c < 3 * m; ++c) ++off[(size_t)tri[c] + 1];
+    for (int32_t v = 0; v < n_vertices; ++v) off[(size_t)v + 1] += off[v];
+    std::vector<int32_t> cur(off.begin(), off.end() - 1);
+    for (int64_t t = 0; t < m; ++t)
+        for (int j = 0; j < 3; ++j) adj[(size_t)cur[tri[3 * t + j]]++] = (int32_t)t;
+}
+
 // Replace positions and velocities of every particle this rank holds (owned and ghost); id_map as in get_state_owned.
 int set_state_from(sb_solver *s, const float *pos, const float *vel, const int32_t *id_map) {
     int rc = set_device(s); if (rc) return rc;
@@ -208,6 +237,67 @@ int sb_set_kinematic_positions(sb_solver *s, const int32_t *ids, const float *po
     return guarded([&]() -> int { return set_kinematic(s, ids, pos, count); });
 }
 
+}  // extern "C"
+
+// sb_readback_begin with an embedding set (SPEC.md 6b), slot k: the skinned visual mesh instead of the particles. The kernel reads the
+// tick-end positions where they are -- the state, or a peek of the T0 tiles that hold a cage particle -- so no particle snapshot is taken.
+static void begin_embedded(sb_solver *s, int k) {
+    sb_solver::Embedding &E = s->emb;
+    const size_t m3 = (size_t)E.m * 3;
+    if (E.dirty) {      // cage in device numbering, the distinct cage particles, incident-triangle lists, the slots' buffers
+        HIP_CHECK(hipStreamSynchronize(s->copy_stream));
+        const std::vector<int32_t> &lof = local_of_old(s);
+        std::vector<int4> cage((size_t)E.m);
+        std::vector<float4> w((size_t)E.m);
+        std::vector<uint8_t> seen((size_t)s->n_local, 0);
+        E.wanted_local.clear();
+        for (int32_t r = 0; r < E.m; ++r) {
+            int32_t l[4];
+            for (int j = 0; j < 4; ++j) {
+                l[j] = lof[(size_t)E.cage[4 * (size_t)r + j]];
+                if (!seen[(size_t)l[j]]) { seen[(size_t)l[j]] = 1; E.wanted_local.push_back(l[j]); }
+            }
+            cage[(size_t)r] = make_int4(l[0], l[1], l[2], l[3]);
+            w[(size_t)r] = make_float4(E.w[4 * (size_t)r], E.w[4 * (size_t)r + 1], E.w[4 * (size_t)r + 2], E.w[4 * (size_t)r + 3]);
+        }
+        E.release();
+        E.d_cage.upload(cage, s->dev_bytes); E.d_w.upload(w, s->dev_bytes);
+        if (!E.tri.empty()) {
+            std::vector<int32_t> off, adj;
+            build_adjacency(E.tri, E.m, off, adj);
+            E.d_tri.upload(E.tri, s->dev_bytes); E.d_adj_off.upload(off, s->dev_bytes); E.d_adj_tri.upload(adj, s->dev_bytes);
+        }
+        for (int q = 0; q < sb_solver::kSnapSlots; ++q) {
+            E.d_pos[q].alloc(m3, s->dev_bytes);
+            HIP_CHECK(hipHostMalloc((void **)&E.h_pos[q], m3 * sizeof(float), hipHostMallocDefault));
+            if (!E.tri.empty()) {
+                E.d_nrm[q].alloc(m3, s->dev_bytes);
+                HIP_CHECK(hipHostMalloc((void **)&E.h_nrm[q], m3 * sizeof(float), hipHostMallocDefault));
+            }
+        }
+        E.dirty = false;
+        s->n_peek_tiles = -1;       // the peek's tile subset follows the cage particles
+    }
+    // skinning on the compute stream (ordered after every tick enqueued so far, before the next one) ...
+    const float *src = render_source(s, /*compact=*/true, E.wanted_local);
+    launch_skin(s->stream, src, E.d_cage.p, E.d_w.p, E.d_pos[k].p, (int)E.m);
+    HIP_CHECK(hipEventRecord(s->ev_snap[k], s->stream));
+    // ... normals (SPEC.md 6a on the skinned array) and D2H on the copy stream
+    HIP_CHECK(hipStreamWaitEvent(s->copy_stream, s->ev_snap[k], 0));
+    HIP_CHECK(hipMemcpyAsync(E.h_pos[k], E.d_pos[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
+    s->snap_has_normals[k] = false;
+    if (!E.tri.empty()) {
+        launch_normals(s->copy_stream, E.d_pos[k].p, E.d_adj_off.p, E.d_adj_tri.p, E.d_tri.p, E.d_nrm[k].p, (int)E.m, nullptr, nullptr);
+        HIP_CHECK(hipMemcpyAsync(E.h_nrm[k], E.d_nrm[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
+        s->snap_has_normals[k] = true;
+    }
+    s->snap_compact[k] = false; s->snap_has_render_set[k] = false; s->snap_embedded[k] = true;
+    HIP_CHECK(hipEventRecord(s->ev_copied[k], s->copy_stream));
+    ++s->snap_pending;
+}
+
+extern "C" {
+
 /* ---- asynchronous render readback -------------------------------------------- */
 
 int sb_readback_begin(sb_solver *s) {
@@ -218,17 +308,24 @@ int sb_readback_begin(sb_solver *s) {
         int rc = set_device(s); if (rc) return rc;
         if (!s->copy_stream) {
             HIP_CHECK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-            if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
             for (int k = 0; k < sb_solver::kSnapSlots; ++k) {
-                s->d_snap[k].alloc((size_t)s->n * 3, s->dev_bytes);
-                HIP_CHECK(hipMemset(s->d_snap[k].p, 0, (size_t)s->n * 3 * sizeof(float)));
-                HIP_CHECK(hipHostMalloc((void **)&s->h_snap[k], (size_t)s->n * 3 * sizeof(float), hipHostMallocDefault));
-                std::memset(s->h_snap[k], 0, (size_t)s->n * 3 * sizeof(float));
                 HIP_CHECK(hipEventCreateWithFlags(&s->ev_snap[k], hipEventDisableTiming));
                 HIP_CHECK(hipEventCreateWithFlags(&s->ev_copied[k], hipEventDisableTiming));
             }
         }
         const int k = (s->snap_head + s->snap_pending) % sb_solver::kSnapSlots;
+        if (s->emb.m > 0) { begin_embedded(s, k); return SB_OK; }       // (no particle snapshot: its n-sized buffers are not even allocated)
+        if (!s->h_snap[sb_solver::kSnapSlots - 1]) {
+            if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
+            for (int q = 0; q < sb_solver::kSnapSlots; ++q) {
+                if (s->h_snap[q]) continue;
+                s->d_snap[q].alloc((size_t)s->n * 3, s->dev_bytes);
+                HIP_CHECK(hipMemset(s->d_snap[q].p, 0, (size_t)s->n * 3 * sizeof(float)));
+                HIP_CHECK(hipHostMalloc((void **)&s->h_snap[q], (size_t)s->n * 3 * sizeof(float), hipHostMallocDefault));
+                std::memset(s->h_snap[q], 0, (size_t)s->n * 3 * sizeof(float));
+            }
+        }
+        s->snap_embedded[k] = false;
         // snapshot on the compute stream (ordered after every tick enqueued so far, before the next one) ...
         const bool compact = s->render_set_only && !s->render_tri.empty();
         // a rank of a partitioned solver serves the render particles it OWNS; vertex normals need the neighbours' particles too and are
@@ -317,7 +414,7 @@ int sb_readback_end(sb_solver *s, const float **pos_xyz_out) {
         const int k = s->snap_head;
         HIP_CHECK(hipEventSynchronize(s->ev_copied[k]));
         check_peer_error(s);       // (the snapshot was taken behind every tick enqueued before it)
-        *pos_xyz_out = s->snap_compact[k] ? s->h_cpos[k] : s->h_snap[k];
+        *pos_xyz_out = s->snap_embedded[k] ? s->emb.h_pos[k] : (s->snap_compact[k] ? s->h_cpos[k] : s->h_snap[k]);
         s->snap_last_ended = k;
         s->snap_head = (s->snap_head + 1) % sb_solver::kSnapSlots; --s->snap_pending;
         return SB_OK;
@@ -328,6 +425,8 @@ int sb_set_render_triangles(sb_solver *s, const int32_t *tri, int32_t m) {
     if (!s || m < 0 || (m > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, "sb_set_render_triangles: bad argument");
     if (s->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_triangles before sb_set_particles");
     if (s->snap_pending) return fail(SB_ERR_STATE, "sb_set_render_triangles while a readback is pending");
+    if (m > 0 && s->emb.m > 0)
+        return fail(SB_ERR_STATE, "sb_set_render_triangles: a render embedding is set (switch it off first: sb_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
         for (int64_t c = 0; c < 3 * (int64_t)m; ++c)
             if (tri[c] < 0 || tri[c] >= s->n) return fail(SB_ERR_INVALID_ARG, "sb_set_render_triangles: particle index out of range");
@@ -340,6 +439,34 @@ int sb_set_render_triangles(sb_solver *s, const int32_t *tri, int32_t m) {
     });
 }
 
+int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri) {
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_render_embedding: null handle");
+    if (s->desc.world > 1)
+        return fail(SB_ERR_UNSUPPORTED, "sb_set_render_embedding: a rank of a partitioned solver does not hold every cage particle; a partitioned body is "
+                    "skinned on the gathered snapshot (sb_group_set_render_embedding)");
+    if (s->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_embedding before sb_set_particles");
+    if (s->snap_pending) return fail(SB_ERR_STATE, "sb_set_render_embedding while a readback is pending");
+    if (m_vertices > 0 && !s->render_tri.empty())
+        return fail(SB_ERR_STATE, "sb_set_render_embedding: render triangles are set (switch them off first: sb_set_render_triangles with m = 0)");
+    return guarded([&]() -> int {
+        if (int rc = check_embedding_args("sb_set_render_embedding", s->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri)) return rc;
+        if (m_vertices == 0 && s->emb.m == 0) return SB_OK;      // off already
+        std::vector<int32_t> cage(cage_ijkl, cage_ijkl + 4 * (size_t)m_vertices), tri(tri_abc, tri_abc + 3 * (size_t)m_tri);
+        std::vector<float> w(weights4, weights4 + 4 * (size_t)m_vertices);
+        if (s->finalized) { int rc = set_device(s); if (rc) return rc; }
+        if (s->copy_stream) HIP_CHECK(hipStreamSynchronize(s->copy_stream));
+        s->emb.release();       // (pointers handed out by earlier readbacks of the embedding end here)
+        s->emb.cage.swap(cage); s->emb.w.swap(w); s->emb.tri.swap(tri);
+        s->emb.m = m_vertices;
+        s->emb.dirty = m_vertices > 0;
+        s->n_peek_tiles = -1;
+        for (bool &b : s->snap_has_normals) b = false;
+        for (bool &b : s->snap_has_render_set) b = false;
+        if (s->snap_last_ended >= 0 && s->snap_embedded[s->snap_last_ended]) s->snap_last_ended = -1;
+        return SB_OK;
+    });
+}
+
 int sb_readback_get_normals(sb_solver *s, const float **out) {
     if (!s || !out) return fail(SB_ERR_INVALID_ARG, "sb_readback_get_normals: null argument");
     if (s->desc.world > 1)
@@ -347,7 +474,7 @@ int sb_readback_get_normals(sb_solver *s, const float **out) {
                     "body are computed on the gathered snapshot (sb_group_readback_get_normals)");
     if (s->snap_last_ended < 0 || !s->snap_has_normals[s->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_readback_get_normals: no finished readback with render triangles set");
-    *out = s->h_nrm[s->snap_last_ended];
+    *out = s->snap_embedded[s->snap_last_ended] ? s->emb.h_nrm[s->snap_last_ended] : s->h_nrm[s->snap_last_ended];
     return SB_OK;
 }
 
@@ -361,6 +488,7 @@ int sb_set_readback_render_set_only(sb_solver *s, int32_t on) {
 
 int sb_readback_get_render_set(sb_solver *s, const int32_t **ids, int32_t *count) {
     if (!s || !ids || !count) return fail(SB_ERR_INVALID_ARG, "sb_readback_get_render_set: null argument");
+    if (s->emb.m > 0) return fail(SB_ERR_STATE, "sb_readback_get_render_set: a render embedding is set (the readback brings render vertices, not particles)");
     if (s->snap_last_ended < 0 || !s->snap_has_render_set[s->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_readback_get_render_set: no finished readback with render triangles set");
     *ids = s->render_set.data();

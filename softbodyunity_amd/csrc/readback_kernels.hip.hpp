@@ -1,4 +1,5 @@
-// readback_kernels.hip.hpp — render readback: snapshots in caller numbering and area-weighted vertex normals (SPEC.md §6a)
+// readback_kernels.hip.hpp — render readback: snapshots in caller numbering, embedded render vertices (SPEC.md §6b) and area-weighted
+// vertex normals (SPEC.md §6a)
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 #pragma once
@@ -32,6 +33,27 @@ __global__ __launch_bounds__(256) void snapshot_compact_kernel(PosView pos, cons
     const float4 p = pv_load(pos, local_of_subset[k]);
     const size_t o = 3 * (size_t)k;
     out_xyz[o] = p.x; out_xyz[o + 1] = p.y; out_xyz[o + 2] = p.z;
+}
+
+// SPEC.md §6b: embedded render vertices. One lane per render vertex r: r = ((w0 x[i0] + w1 x[i1]) + w2 x[i2]) + w3 x[i3], every product
+// rounded, the sums left to right (the unit is built with contraction off). src_xyz is any packed xyz array the cage indexes: the state
+// or the peek array in device numbering (the solver translates the cage once), or a gathered snapshot in whole-mesh numbering (the
+// group). A bandwidth-bound gather: 16 B of cage and 16 B of weights per lane, coalesced; four 12-byte reads wherever the cage points
+// (neighbouring render vertices share cages, so most of them are served by the L2); 12 B out, in the caller's vertex order.
+__global__ __launch_bounds__(256) void skin_kernel(const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= m) return;
+    const int4 c = cage[r];
+    const float4 w = weights[r];
+    const size_t a0 = 3 * (size_t)c.x, a1 = 3 * (size_t)c.y, a2 = 3 * (size_t)c.z, a3 = 3 * (size_t)c.w;
+    const V3 x0 = {src_xyz[a0], src_xyz[a0 + 1], src_xyz[a0 + 2]};
+    const V3 x1 = {src_xyz[a1], src_xyz[a1 + 1], src_xyz[a1 + 2]};
+    const V3 x2 = {src_xyz[a2], src_xyz[a2 + 1], src_xyz[a2 + 2]};
+    const V3 x3 = {src_xyz[a3], src_xyz[a3 + 1], src_xyz[a3 + 2]};
+    const size_t o = 3 * (size_t)r;
+    out_xyz[o] = ((w.x * x0.x + w.y * x1.x) + w.z * x2.x) + w.w * x3.x;
+    out_xyz[o + 1] = ((w.x * x0.y + w.y * x1.y) + w.z * x2.y) + w.w * x3.y;
+    out_xyz[o + 2] = ((w.x * x0.z + w.y * x1.z) + w.z * x2.z) + w.w * x3.z;
 }
 
 // SPEC.md §6a: area-weighted vertex normals on a position snapshot in caller numbering. One lane per vertex gathers its

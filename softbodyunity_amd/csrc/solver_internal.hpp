@@ -288,6 +288,30 @@ struct sb_solver {
     bool snap_has_render_set[kSnapSlots] = {false, false, false};
     std::vector<int32_t> render_local;     // device numbering of render_set's particles
     int snap_last_ended = -1;
+    // embedded render vertices (sb_set_render_embedding, SPEC.md 6b): while emb_m > 0 a readback brings the skinned visual mesh instead of
+    // the particles. Excludes the render triangles above (either mode is switched off before the other is set).
+    struct Embedding {
+        int32_t m = 0;                         // render vertices (0 = off)
+        std::vector<int32_t> cage, tri;        // as given: 4 particles per vertex (caller numbering), triangles over the render vertices
+        std::vector<float> w;                  // 4 weights per vertex
+        bool dirty = false;                    // changed since the last upload
+        std::vector<int32_t> wanted_local;     // the distinct cage particles, device numbering: what a peek has to cover
+        DevBuf<int4> d_cage;                   // device numbering (translated once through local_of_old)
+        DevBuf<float4> d_w;
+        DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri;
+        DevBuf<float> d_pos[kSnapSlots], d_nrm[kSnapSlots];
+        float *h_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
+        void release() {                       // device and pinned buffers (no readback is pending when the embedding changes)
+            d_cage.free(); d_w.free(); d_tri.free(); d_adj_off.free(); d_adj_tri.free();
+            for (int k = 0; k < kSnapSlots; ++k) {
+                d_pos[k].free(); d_nrm[k].free();
+                if (h_pos[k]) (void)hipHostFree(h_pos[k]);
+                if (h_nrm[k]) (void)hipHostFree(h_nrm[k]);
+                h_pos[k] = h_nrm[k] = nullptr;
+            }
+        }
+    } emb;
+    bool snap_embedded[kSnapSlots] = {false, false, false};
     // kinematic targets (sb_set_kinematic_positions): a ring of pinned host tables the scatter kernel reads directly; a table is reused
     // only after the kernel that read it has finished (its event)
     static constexpr int kKinSlots = 4;
@@ -350,6 +374,7 @@ struct sb_solver {
             if (ev_snap[k]) (void)hipEventDestroy(ev_snap[k]);
             if (ev_copied[k]) (void)hipEventDestroy(ev_copied[k]);
         }
+        emb.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (int k = 0; k < kKinSlots; ++k) {
             if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
@@ -405,6 +430,11 @@ void launch_snapshot_all(sb_solver *s, const float *src_xyz, const int32_t *d_ta
 void launch_snapshot_subset(sb_solver *s, const float *src_xyz, const int32_t *d_ids, const int32_t *d_local, int count, float *dst_xyz);
 void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, float *nrm_xyz, int count,
                     const int32_t *subset, float *subset_pos_xyz);
+void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m);
+// sb_set_render_embedding / sb_group_set_render_embedding: the argument rules both share (n = particles the cage may name)
+int check_embedding_args(const char *who, int32_t n, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri);
+// incident-triangle lists per vertex, triangle ids ascending (what normals_kernel walks)
+void build_adjacency(const std::vector<int32_t> &tri, int32_t n_vertices, std::vector<int32_t> &off, std::vector<int32_t> &adj);
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

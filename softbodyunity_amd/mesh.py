@@ -305,6 +305,64 @@ def from_triangle_mesh(vertices, triangles, weld_eps=1e-6, label="surface_mesh")
     return m, particle_of_vertex.astype(np.int32)
 
 
+def embed_vertices(nodes, tets, vertices):
+    """Bind a visual mesh to a tet cage (SPEC.md 6b): -> (cage_ijkl int32 (m,4), weights float32 (m,4)).
+
+    For each vertex the tet that contains it in the rest pose (row of `tets`, its corner order kept) and the vertex' barycentric
+    coordinates in it, computed in float64 and cast at the end. A vertex inside no tet takes the tet whose smallest barycentric
+    coordinate is largest: that tet extrapolates, some weights are negative. The tets searched for a vertex are those incident to
+    its nearest cage nodes, nearest first (a k-d tree over the nodes); the search of a vertex ends with the first tet that holds it."""
+    from scipy.spatial import cKDTree
+    P = np.asarray(nodes, np.float64).reshape(-1, 3)
+    T = np.asarray(tets, np.int64).reshape(-1, 4)
+    V = np.asarray(vertices, np.float64).reshape(-1, 3)
+    m = V.shape[0]
+    assert T.shape[0] > 0 and T.min() >= 0 and T.max() < P.shape[0]
+    # per tet: lambda_1..3 = A^-1 (v - p0), lambda_0 = 1 - their sum
+    p0 = P[T[:, 0]]
+    A = np.stack([P[T[:, 1]] - p0, P[T[:, 2]] - p0, P[T[:, 3]] - p0], axis=2)
+    det = np.linalg.det(A)
+    ok = np.abs(det) > 0.0
+    Ainv = np.zeros_like(A)
+    Ainv[ok] = np.linalg.inv(A[ok])
+    # node -> incident (non-degenerate) tets, CSR
+    flat_node = T[ok].ravel(); flat_tet = np.repeat(np.nonzero(ok)[0], 4)
+    order = np.argsort(flat_node, kind="stable")
+    inc_tet = flat_tet[order]
+    inc_off = np.concatenate([[0], np.cumsum(np.bincount(flat_node, minlength=P.shape[0]))])
+    used = np.nonzero(np.diff(inc_off) > 0)[0]                  # nodes no tet uses cannot lead to one
+    assert used.size, "every tet is degenerate"
+    k = int(min(12, used.size))
+    _, near = cKDTree(P[used]).query(V, k=k)
+    near = used[np.asarray(near).reshape(m, k)]
+    best_min = np.full(m, -np.inf)
+    best_tet = np.zeros(m, np.int64)
+    best_w = np.zeros((m, 4))
+    eps = 1e-12                                                 # inside: every coordinate >= -eps (vertices ON a face or a node count as inside)
+    for j in range(k):
+        todo = np.nonzero(best_min < -eps)[0]
+        if todo.size == 0:
+            break
+        for lo in range(0, todo.size, 1 << 16):                 # (bounded scratch: ~25 candidate tets per vertex and node)
+            vs = todo[lo:lo + (1 << 16)]
+            node = near[vs, j]
+            cnt = inc_off[node + 1] - inc_off[node]
+            seg = np.concatenate([[0], np.cumsum(cnt)])
+            pair_v = np.repeat(np.arange(vs.size), cnt)
+            pair_t = inc_tet[np.repeat(inc_off[node], cnt) + (np.arange(seg[-1]) - np.repeat(seg[:-1], cnt))]
+            lam = np.einsum("pij,pj->pi", Ainv[pair_t], V[vs[pair_v]] - p0[pair_t])
+            w4 = np.concatenate([1.0 - lam.sum(axis=1, keepdims=True), lam], axis=1)
+            mn = w4.min(axis=1)
+            seg_max = np.maximum.reduceat(mn, seg[:-1])
+            hit = np.nonzero(mn == seg_max[pair_v])[0]
+            _, first = np.unique(pair_v[hit], return_index=True)      # first best candidate per vertex
+            pick = hit[first]
+            better = seg_max > best_min[vs]
+            sel = vs[better]
+            best_min[sel] = seg_max[better]; best_tet[sel] = pair_t[pick[better]]; best_w[sel] = w4[pick[better]]
+    return T[best_tet].astype(np.int32), best_w.astype(np.float32)
+
+
 def read_tetgen(node_path, ele_path):
     """TetGen .node/.ele pair -> from_tet_mesh (so a real Stanford-bunny tet mesh can replace the surrogate)."""
     def rows(path):

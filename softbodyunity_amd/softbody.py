@@ -47,6 +47,7 @@ class Softbody:
         self._cpu_plan = None
         self._h = None
         self._render_set_only = False
+        self._embedded = 0    # render vertices of the embedding in force (set_render_embedding), 0 = none
         self.vertices = None  # what the C# component assigns to mesh.vertices after each FixedUpdate
 
     # ---- MonoBehaviour surface ------------------------------------------------------------------
@@ -179,11 +180,14 @@ class Softbody:
     def readback_end(self, normals=False):
         """-> (N,3) float32 view of the plugin's pinned snapshot (valid until the second readback_begin after it);
         with normals=True -> (positions, vertex normals) -- needs set_render_triangles (SPEC.md 6a). In render-set-only
-        mode both arrays are compact, (count,3), entry k belonging to particle render_set()[k]."""
+        mode both arrays are compact, (count,3), entry k belonging to particle render_set()[k]. With an embedding set
+        (set_render_embedding) both arrays are (m,3): the skinned render vertices and their normals, in the caller's vertex order."""
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_readback_end(self._h, C.byref(p)))
         rows = self.n
-        if self._render_set_only:
+        if self._embedded:
+            rows = self._embedded
+        elif self._render_set_only:
             rows = len(self.render_set())
         pos = np.ctypeslib.as_array(p, shape=(rows, 3))
         if not normals:
@@ -207,6 +211,14 @@ class Softbody:
         """Render triangles (M,3) particle indices: every later readback also brings area-weighted vertex normals."""
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
         check(native.lib().sb_set_render_triangles(self._h, tri.ctypes.data_as(C.POINTER(C.c_int32)), tri.shape[0]))
+
+    def set_render_embedding(self, cage, weights, tri=None):
+        """Embedded render vertices (SPEC.md 6b): vertex r = sum_j weights[r, j] * x[cage[r, j]] (mesh.embed_vertices makes both from a
+        visual mesh). Every later readback brings the (m,3) skinned vertices instead of the particles, and -- with tri, (M,3) indices of
+        RENDER VERTICES -- their normals. cage=None (or m = 0) switches the embedding off."""
+        cage, weights, tri, m = _embedding_args(cage, weights, tri)
+        check(native.lib().sb_set_render_embedding(self._h, _ip(cage), _fp(weights), m, _ip(tri), 0 if tri is None else tri.shape[0]))
+        self._embedded = m
 
     def set_kinematic_positions(self, ids, pos):
         """Move pinned particles (inverse mass 0) to new positions between two ticks (SPEC.md 2, attachments)."""
@@ -270,6 +282,26 @@ class Softbody:
         return ms.value
 
 
+def _embedding_args(cage, weights, tri):
+    """-> (cage (m,4) int32, weights (m,4) float32, tri (M,3) int32 or None, m) as the C entry points take them"""
+    if cage is None:
+        return None, None, None, 0
+    cage = np.ascontiguousarray(cage, dtype=np.int32).reshape(-1, 4)
+    weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+    assert cage.shape == weights.shape, "one row of four weights per row of four cage particles"
+    if tri is not None:
+        tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+    return cage, weights, tri, cage.shape[0]
+
+
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _fp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
 def comm_unique_id():
     buf = (C.c_uint8 * native.SB_UNIQUE_ID_BYTES)()
     check(native.lib().sb_comm_unique_id(buf))
@@ -299,6 +331,7 @@ class SoftbodyGroup:
         self.tuning = tuning
         self._g = None
         self._render_set_only = False
+        self._embedded = 0
         self.vertices = None
 
     def Start(self):
@@ -390,6 +423,12 @@ class SoftbodyGroup:
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
         check(native.lib().sb_group_set_render_triangles(self._g, tri.ctypes.data_as(C.POINTER(C.c_int32)), tri.shape[0]))
 
+    def set_render_embedding(self, cage, weights, tri=None):
+        """Softbody.set_render_embedding on the gathered snapshot: cage indices in the whole mesh's numbering."""
+        cage, weights, tri, m = _embedding_args(cage, weights, tri)
+        check(native.lib().sb_group_set_render_embedding(self._g, _ip(cage), _fp(weights), m, _ip(tri), 0 if tri is None else tri.shape[0]))
+        self._embedded = m
+
     def set_readback_render_set_only(self, on=True):
         check(native.lib().sb_group_set_readback_render_set_only(self._g, 1 if on else 0))
         self._render_set_only = bool(on)
@@ -405,7 +444,7 @@ class SoftbodyGroup:
     def readback_end(self, normals=False):
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_group_readback_end(self._g, C.byref(p)))
-        rows = len(self.render_set()) if self._render_set_only else self.n
+        rows = self._embedded if self._embedded else (len(self.render_set()) if self._render_set_only else self.n)
         pos = np.ctypeslib.as_array(p, shape=(rows, 3))
         if not normals:
             return pos
