@@ -2,7 +2,7 @@
 //
 // Start()       -> sb_group_create + sb_group_set_particles/sb_group_set_*_constraints + sb_group_finalize   (plan, partition, upload)
 // FixedUpdate() -> sb_group_step(Time.fixedDeltaTime, substeps) + sb_group_get_positions                     (one tick, SPEC.md §2)
-//                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals instead (one tick of latency, no stall)
+//                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) instead (one tick of latency, no stall)
 // OnDestroy()   -> sb_group_destroy
 //
 // A Unity player is ONE process: the component talks to the plugin through include/softbody_group.h, where `deviceCount` GPUs sit
@@ -67,12 +67,15 @@ namespace SoftbodyMI355X
         public int[] volumeIJKL; public float[] volumeRest;
         public int[] bendingIJKL; public float[] bendingRestCosSin;
         public int[] renderTriangles;          // particle indices, 3 per triangle (SoftbodyMeshBuilder: mesh.triangles through particleOfVertex)
+        [Tooltip("Optional, with renderTriangles: one UV per PARTICLE. The GPU then also computes vertex tangents for normal mapping (SPEC.md 6c). A mesh with UV seams needs visualMesh instead.")]
+        [SerializeField] Vector2[] renderUV = null;
 
         IntPtr handle = IntPtr.Zero;
         SoftbodyCpuSolver cpu;
         Mesh mesh;
         GCHandle posPin;
         Vector3[] normals;
+        Vector4[] tangents;                    // non-null: UVs were handed over (sb_group_set_render_uvs) and every readback brings tangents
         bool snapshotPending;
 
         void Start()
@@ -154,11 +157,25 @@ namespace SoftbodyMI355X
                 positions = (Vector3[])visual.Clone(); normals = new Vector3[visual.Length];      // (what FixedUpdate copies the snapshot into)
                 posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
                 mesh.Clear(); mesh.vertices = positions; mesh.triangles = visualTri; mesh.uv = visualMesh.uv;
+                Vector2[] visualUV = visualMesh.uv;
+                if (visualUV != null && visualUV.Length == visual.Length && visualTri.Length >= 3)
+                {
+                    // tangents for normal mapping, on the GPU beside the normals (instead of Mesh.RecalculateTangents every FixedUpdate)
+                    Pin(visualUV, uv => SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_uvs(handle, uv, visualUV.Length), "sb_group_set_render_uvs"));
+                    tangents = new Vector4[visual.Length];
+                }
             }
             else if (asyncReadback && renderTriangles != null && renderTriangles.Length >= 3)
             {
                 SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_triangles(handle, renderTriangles, renderTriangles.Length / 3), "sb_group_set_render_triangles");
                 normals = new Vector3[positions.Length];
+                bool withUV = renderUV != null && renderUV.Length == positions.Length;      // one UV per particle (no seams in this mode)
+                if (withUV)
+                {
+                    Pin(renderUV, uv => SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_uvs(handle, uv, renderUV.Length), "sb_group_set_render_uvs"));
+                    tangents = new Vector4[positions.Length];
+                    mesh.uv = renderUV;
+                }
                 if (renderSetOnly)
                 {
                     // the plugin's render set = the particles the triangles use, ascending: rebuild the mesh over exactly that set
@@ -166,13 +183,15 @@ namespace SoftbodyMI355X
                     var used = new System.Collections.Generic.SortedSet<int>(renderTriangles);
                     var compactOf = new System.Collections.Generic.Dictionary<int, int>();
                     var compactPos = new Vector3[used.Count];
-                    foreach (int p in used) { compactPos[compactOf.Count] = positions[p]; compactOf[p] = compactOf.Count; }
+                    var compactUV = withUV ? new Vector2[used.Count] : null;
+                    foreach (int p in used) { compactPos[compactOf.Count] = positions[p]; if (withUV) compactUV[compactOf.Count] = renderUV[p]; compactOf[p] = compactOf.Count; }
                     var tri = new int[renderTriangles.Length];
                     for (int k = 0; k < tri.Length; ++k) tri[k] = compactOf[renderTriangles[k]];
                     posPin.Free();
                     positions = compactPos; normals = new Vector3[compactPos.Length];
                     posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
                     mesh.Clear(); mesh.vertices = positions; mesh.triangles = tri;
+                    if (withUV) { mesh.uv = compactUV; tangents = new Vector4[compactPos.Length]; }
                 }
             }
         }
@@ -194,10 +213,16 @@ namespace SoftbodyMI355X
                         SoftbodyNative.Check(SoftbodyNative.sb_group_readback_get_normals(handle, out IntPtr nrm), "sb_group_readback_get_normals");
                         CopyVectors(nrm, normals);
                     }
+                    if (tangents != null)
+                    {
+                        SoftbodyNative.Check(SoftbodyNative.sb_group_readback_get_tangents(handle, out IntPtr tan), "sb_group_readback_get_tangents");
+                        CopyVectors4(tan, tangents);
+                    }
                 }
                 snapshotPending = true;
                 mesh.vertices = positions;
                 if (normals != null) mesh.normals = normals; else mesh.RecalculateNormals();
+                if (tangents != null) mesh.tangents = tangents;
                 return;
             }
             if (useGpu)
@@ -273,6 +298,11 @@ namespace SoftbodyMI355X
         static unsafe void CopyVectors(IntPtr src, Vector3[] dst)
         {
             fixed (Vector3* d = dst) Buffer.MemoryCopy((void*)src, d, (long)dst.Length * 12, (long)dst.Length * 12);
+        }
+
+        static unsafe void CopyVectors4(IntPtr src, Vector4[] dst)
+        {
+            fixed (Vector4* d = dst) Buffer.MemoryCopy((void*)src, d, (long)dst.Length * 16, (long)dst.Length * 16);
         }
 
         static void Pin<T>(T[] a, Action<IntPtr> f)

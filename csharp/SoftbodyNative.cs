@@ -160,6 +160,9 @@ namespace SoftbodyMI355X
         // embedded render vertices (SPEC.md 6b): cageIjkl 4 particle indices and weights4 4 floats per render vertex, triAbc over RENDER VERTICES (may be null with mTri = 0)
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_embedding(IntPtr s, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_normals(IntPtr s, out IntPtr normalXyz);
+        // render tangents (SPEC.md 6c): uv = 2 floats per vertex of the render mode in force (a pinned Vector2[]); tangents = Vector4 per row (xyz, handedness)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_uvs(IntPtr s, IntPtr uv, int count);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_tangents(IntPtr s, out IntPtr tangentXyzw);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_render_set_only(IntPtr s, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_render_set(IntPtr s, out IntPtr ids, out int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_get_owner(IntPtr s, IntPtr ownerRankOut, int n);
@@ -213,10 +216,12 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_kinematic_positions(IntPtr g, IntPtr ids, IntPtr posXyz, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_triangles(IntPtr g, int[] triAbc, int m);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_embedding(IntPtr g, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_uvs(IntPtr g, IntPtr uv, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_readback_render_set_only(IntPtr g, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_begin(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_end(IntPtr g, out IntPtr posXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_normals(IntPtr g, out IntPtr normalXyz);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_tangents(IntPtr g, out IntPtr tangentXyzw);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_render_set(IntPtr g, out IntPtr ids, out int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_rank_count(IntPtr g);

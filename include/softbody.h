@@ -21,7 +21,7 @@
  *    SB_ERR_NO_DEVICE.
  *  - Semantics of one tick: SPEC.md.
  *
- * This header is the whole PRODUCT surface of a solver handle (32 functions). Beside it:
+ * This header is the whole PRODUCT surface of a solver handle (35 functions). Beside it:
  *   softbody_group.h  one process -- a Unity player -- driving several GPUs behind the same component (sb_group_*)
  *   softbody_plan.h   host-only planner inspection (published order, tiles, halo lists; frame / window of sharded authoring)
  *   softbody_debug.h  test hooks, the table validator, per-launch timing and the tuning switches of A/B measurements
@@ -234,6 +234,26 @@ int sb_readback_get_render_set(sb_solver *s, const int32_t **ids_out, int32_t *c
  * sb_set_particles, not while a readback is pending. */
 int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices,
                             const int32_t *tri_abc, int32_t m_tri);
+/* Render tangents (SPEC.md 6c; replaces Unity's Mesh.RecalculateTangents on the main thread): give one (u, v) pair per vertex of the render
+ * mode in force -- 2*count floats, indexed like that mode's triangles: count = n (one pair per particle) while render triangles are set, count =
+ * m_vertices while an embedding with m_tri > 0 is set. The plugin copies the array and computes the per-triangle coefficients of SPEC.md 6c from
+ * it. Every later sb_readback_begin then computes normals AND tangents in one kernel on the copy stream (the normals are bit for bit those of a
+ * readback without UVs) and brings the tangents to pinned memory; after the matching sb_readback_end, sb_readback_get_tangents returns rows*4
+ * floats -- rows as for the normals: n, the render set's count, or m_vertices -- (x, y, z, w) per vertex, Unity's Vector4: xyz the unit tangent
+ * (zero where it is undefined), w = +-1 the handedness, bitangent = cross(normal, tangent) * w; (0, 0, 0, 1) for a vertex in no triangle or
+ * only in UV-degenerate ones. The pointer is valid exactly as long as that snapshot's normals.
+ *  - count = 0 (uv may be NULL) switches tangents off; so does EVERY accepted call of sb_set_render_triangles or sb_set_render_embedding,
+ *    whatever its arguments: UVs belong to the triangle list they were given for, and are given again after it.
+ *  - No render mode with triangles set (neither render triangles, nor an embedding with m_tri > 0) and count > 0: SB_ERR_STATE. A count other than
+ *    the mode's, a NULL uv with count > 0, a NaN or infinite UV: SB_ERR_INVALID_ARG, and nothing is changed (the UVs in force stay in force).
+ *    While a readback is pending: SB_ERR_STATE. Before or after sb_finalize.
+ *  - sb_readback_get_tangents when the snapshot ended last was taken without UVs: SB_ERR_STATE.
+ *  - A rank of a partitioned solver (world > 1) returns SB_ERR_UNSUPPORTED from both calls, for the reason sb_readback_get_normals does
+ *    (sb_group_set_render_uvs / sb_group_readback_get_tangents serve that case).
+ * In render-triangle mode vertices are particles, so a UV seam cannot be expressed; a mesh with seams goes through the embedding, whose render
+ * vertices may be duplicated freely. */
+int sb_set_render_uvs(sb_solver *s, const float *uv /* 2 floats per vertex */, int32_t count);
+int sb_readback_get_tangents(sb_solver *s, const float **tangent_xyzw_out);
 int sb_get_owner(sb_solver *s, int32_t *owner_rank_out, int32_t n);
 
 

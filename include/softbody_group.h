@@ -100,9 +100,14 @@ int sb_group_set_readback_render_set_only(sb_group *g, int32_t render_set_only);
  * validation, same exclusion against sb_group_set_render_triangles. */
 int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices,
                                   const int32_t *tri_abc, int32_t m_tri);
+/* Render tangents (sb_set_render_uvs / sb_readback_get_tangents, SPEC.md 6c; UVs indexed by whole-mesh particle, or by render vertex of the
+ * embedding): the same contract on the gathered snapshot -- the render device computes normals and tangents in one kernel after the gather, in
+ * all three modes (full, render-set-only, embedded). Nothing changes on the ranks. */
+int sb_group_set_render_uvs(sb_group *g, const float *uv /* 2 floats per vertex */, int32_t count);
 int sb_group_readback_begin(sb_group *g);
 int sb_group_readback_end(sb_group *g, const float **pos_xyz_out);
 int sb_group_readback_get_normals(sb_group *g, const float **normal_xyz_out);
+int sb_group_readback_get_tangents(sb_group *g, const float **tangent_xyzw_out);
 int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids_out, int32_t *count_out);
 
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */

@@ -125,6 +125,7 @@ struct sb_group {
     DevBuf<float> d_emb_pos[kSnapSlots], d_emb_nrm[kSnapSlots];
     float *h_emb_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_emb_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
     bool snap_embedded[kSnapSlots] = {false, false, false};
+    RenderTangents tan;                          // render tangents of either mode (sb_group_set_render_uvs, SPEC.md 6c), on the render device
     void release_embedding() {                   // on the render device; no readback is pending when the embedding changes
         d_emb_cage.free(); d_emb_w.free(); d_emb_tri.free(); d_emb_adj_off.free(); d_emb_adj_tri.free();
         for (int k = 0; k < kSnapSlots; ++k) {
@@ -168,6 +169,7 @@ struct sb_group {
         }
         d_tri.free(); d_adj_off.free(); d_adj_tri.free(); d_render_set.free();
         release_embedding();
+        tan.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (size_t r = 0; r < rr.size(); ++r) {
             (void)hipSetDevice(devices[r]);
@@ -666,6 +668,8 @@ int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {
         return fail(SB_ERR_STATE, "sb_group_set_render_triangles: a render embedding is set (switch it off first: sb_group_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
         for (int64_t c = 0; c < 3 * (int64_t)m; ++c) if (tri[c] < 0 || tri[c] >= g->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: particle index out of range");
+        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        g->tan.clear();         // every call that is accepted clears the UVs (sb_group_set_render_uvs)
         g->render_tri.assign(tri, tri + 3 * (size_t)m);
         g->render_dirty = true;
         if (m == 0) g->render_set_only = false;
@@ -682,6 +686,8 @@ int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const f
         return fail(SB_ERR_STATE, "sb_group_set_render_embedding: render triangles are set (switch them off first: sb_group_set_render_triangles with m = 0)");
     return guarded([&]() -> int {
         if (int rc = check_embedding_args("sb_group_set_render_embedding", g->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri)) return rc;
+        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        g->tan.clear();         // every call that is accepted clears the UVs (sb_group_set_render_uvs)
         if (m_vertices == 0 && g->emb_m == 0) return SB_OK;      // off already
         std::vector<int32_t> cage(cage_ijkl, cage_ijkl + 4 * (size_t)m_vertices), tri(tri_abc, tri_abc + 3 * (size_t)m_tri);
         std::vector<float> w(weights4, weights4 + 4 * (size_t)m_vertices);
@@ -697,6 +703,15 @@ int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const f
         for (bool &b : g->snap_has_normals) b = false;
         if (g->snap_last_ended >= 0 && g->snap_embedded[g->snap_last_ended]) g->snap_last_ended = -1;
         return SB_OK;
+    });
+}
+
+int sb_group_set_render_uvs(sb_group *g, const float *uv, int32_t count) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_uvs: null group");
+    return guarded([&]() -> int {
+        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        const int64_t rows = !g->render_tri.empty() ? (int64_t)g->n : (g->emb_m > 0 && !g->emb_tri.empty() ? (int64_t)g->emb_m : -1);
+        return set_render_uvs("sb_group_set_render_uvs", g->tan, uv, count, rows, g->snap_pending != 0);
     });
 }
 
@@ -830,9 +845,16 @@ int sb_group_readback_begin(sb_group *g) {
             for (int r = 0; r < W; ++r) HIP_CHECK(hipStreamWaitEvent(g->copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
             launch_skin(g->copy_stream, gather, g->d_emb_cage.p, g->d_emb_w.p, g->d_emb_pos[k].p, (int)g->emb_m);
             HIP_CHECK(hipMemcpyAsync(g->h_emb_pos[k], g->d_emb_pos[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-            g->snap_has_normals[k] = false;
+            g->snap_has_normals[k] = false; g->tan.snap_has[k] = false;
             if (!g->emb_tri.empty()) {
-                launch_normals(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->d_emb_nrm[k].p, (int)g->emb_m, nullptr, nullptr);
+                if (g->tan.on()) {      // SPEC.md 6c: normals and tangents in one walk
+                    g->tan.prepare(g->emb_tri, (size_t)g->emb_m, g->dev_bytes);
+                    launch_normals_tangents(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->tan.d_k.p, g->d_emb_nrm[k].p,
+                                            g->tan.d_tan[k].p, (int)g->emb_m, nullptr, nullptr);
+                    HIP_CHECK(hipMemcpyAsync(g->tan.h_tan[k], g->tan.d_tan[k].p, (size_t)g->emb_m * sizeof(float4), hipMemcpyDeviceToHost, g->copy_stream));
+                    g->tan.snap_has[k] = true;
+                } else
+                    launch_normals(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->d_emb_nrm[k].p, (int)g->emb_m, nullptr, nullptr);
                 HIP_CHECK(hipMemcpyAsync(g->h_emb_nrm[k], g->d_emb_nrm[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
                 g->snap_has_normals[k] = true;
             }
@@ -862,6 +884,7 @@ int sb_group_readback_begin(sb_group *g) {
                 }
                 if (!g->h_cpos[k]) HIP_CHECK(hipHostMalloc((void **)&g->h_cpos[k], std::max<size_t>(g->h_cpos_cap, 3) * sizeof(float), hipHostMallocDefault));
             }
+            if (g->tan.on()) g->tan.prepare(g->render_tri, cnt3 / 3, g->dev_bytes);      // (a larger need frees the slots' buffers, as for the normals)
         }
         // every rank: tick-end positions (peek or completed tick) of what it owns, straight into the gather buffer on the render device
         float *dst = g->d_gather[k].p;
@@ -881,12 +904,18 @@ int sb_group_readback_begin(sb_group *g) {
         HIP_CHECK(hipSetDevice(dev0));
         for (int r = 0; r < W; ++r) HIP_CHECK(hipStreamWaitEvent(g->copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
         if (!compact) HIP_CHECK(hipMemcpyAsync(g->h_pos[k], g->d_gather[k].p, n3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-        g->snap_has_normals[k] = false;
+        g->snap_has_normals[k] = false; g->tan.snap_has[k] = false;
         g->snap_compact[k] = compact;
         if (!g->render_tri.empty()) {
             const int count = compact ? (int)g->render_set.size() : (int)g->n;
-            launch_normals(g->copy_stream, g->d_gather[k].p, g->d_adj_off.p, g->d_adj_tri.p, g->d_tri.p, g->d_nrm[k].p, count,
-                           compact ? g->d_render_set.p : (const int32_t *)nullptr, compact ? g->d_cpos[k].p : (float *)nullptr);
+            if (g->tan.on()) {      // SPEC.md 6c: normals and tangents in one walk
+                launch_normals_tangents(g->copy_stream, g->d_gather[k].p, g->d_adj_off.p, g->d_adj_tri.p, g->d_tri.p, g->tan.d_k.p, g->d_nrm[k].p, g->tan.d_tan[k].p, count,
+                                        compact ? g->d_render_set.p : (const int32_t *)nullptr, compact ? g->d_cpos[k].p : (float *)nullptr);
+                HIP_CHECK(hipMemcpyAsync(g->tan.h_tan[k], g->tan.d_tan[k].p, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost, g->copy_stream));
+                g->tan.snap_has[k] = true;
+            } else
+                launch_normals(g->copy_stream, g->d_gather[k].p, g->d_adj_off.p, g->d_adj_tri.p, g->d_tri.p, g->d_nrm[k].p, count,
+                               compact ? g->d_render_set.p : (const int32_t *)nullptr, compact ? g->d_cpos[k].p : (float *)nullptr);
             HIP_CHECK(hipMemcpyAsync(g->h_nrm[k], g->d_nrm[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
             if (compact) HIP_CHECK(hipMemcpyAsync(g->h_cpos[k], g->d_cpos[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
             g->snap_has_normals[k] = true;
@@ -917,6 +946,14 @@ int sb_group_readback_get_normals(sb_group *g, const float **out) {
     if (g->snap_last_ended < 0 || !g->snap_has_normals[g->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_group_readback_get_normals: no finished readback with render triangles set");
     *out = g->snap_embedded[g->snap_last_ended] ? g->h_emb_nrm[g->snap_last_ended] : g->h_nrm[g->snap_last_ended];
+    return SB_OK;
+}
+
+int sb_group_readback_get_tangents(sb_group *g, const float **out) {
+    if (!g || !out) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_tangents: null argument");
+    if (g->snap_last_ended < 0 || !g->tan.snap_has[g->snap_last_ended])
+        return fail(SB_ERR_STATE, "sb_group_readback_get_tangents: no finished readback with render UVs set");
+    *out = reinterpret_cast<const float *>(g->tan.h_tan[g->snap_last_ended]);
     return SB_OK;
 }
 

@@ -1,4 +1,4 @@
-// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals and embedded render vertices
+// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals, tangents and embedded render vertices
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
@@ -121,6 +121,13 @@ void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_of
     hipLaunchKernelGGL(sbk::normals_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, snap_xyz, adj_off, adj_tri, tri, nrm_xyz, count, subset, subset_pos_xyz);
     HIP_CHECK(hipGetLastError());
 }
+void launch_normals_tangents(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, const float4 *tri_k,
+                             float *nrm_xyz, float4 *tan_xyzw, int count, const int32_t *subset, float *subset_pos_xyz) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(sbk::normals_tangents_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, snap_xyz, adj_off, adj_tri, tri, tri_k, nrm_xyz, tan_xyzw,
+                       count, subset, subset_pos_xyz);
+    HIP_CHECK(hipGetLastError());
+}
 
 void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m) {
     if (m <= 0) return;
@@ -138,6 +145,53 @@ int check_embedding_args(const char *who, int32_t n, const int32_t *cage, const 
     }
     for (int64_t c = 0; c < 3 * (int64_t)m_tri; ++c)
         if (tri[c] < 0 || tri[c] >= m) return fail(SB_ERR_INVALID_ARG, me + ": triangle index out of range (triangles index render vertices)");
+    return SB_OK;
+}
+
+// SPEC.md 6c, static part. Host code of a unit built with contraction off: two rounded products and one subtraction for det, four IEEE divisions.
+void tangent_coefficients(const std::vector<float> &uv, const std::vector<int32_t> &tri, std::vector<float4> &k) {
+    const size_t m = tri.size() / 3;
+    k.resize(m);
+    for (size_t t = 0; t < m; ++t) {
+        const size_t a = 2 * (size_t)tri[3 * t], b = 2 * (size_t)tri[3 * t + 1], c = 2 * (size_t)tri[3 * t + 2];
+        const float du1 = uv[b] - uv[a], dv1 = uv[b + 1] - uv[a + 1], du2 = uv[c] - uv[a], dv2 = uv[c + 1] - uv[a + 1];
+        const float p0 = du1 * dv2, p1 = du2 * dv1;
+        const float det = p0 - p1;
+        const float k0 = dv2 / det, k1 = dv1 / det, k2 = du1 / det, k3 = du2 / det;
+        const bool ok = det != 0.0f && std::isfinite(k0) && std::isfinite(k1) && std::isfinite(k2) && std::isfinite(k3);
+        k[t] = ok ? make_float4(k0, k1, k2, k3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // a UV-degenerate triangle contributes zeros
+    }
+}
+
+void RenderTangents::prepare(const std::vector<int32_t> &tri, size_t n_rows, int64_t &acct) {
+    if (dirty) {
+        std::vector<float4> k;
+        tangent_coefficients(uv, tri, k);
+        d_k.upload(k, acct);
+        dirty = false;
+    }
+    if (rows < n_rows || !h_tan[kSlots - 1]) {
+        for (int q = 0; q < kSlots; ++q) {
+            if (h_tan[q]) { (void)hipHostFree(h_tan[q]); h_tan[q] = nullptr; }
+            d_tan[q].alloc(n_rows, acct);
+            HIP_CHECK(hipHostMalloc((void **)&h_tan[q], std::max<size_t>(n_rows, 1) * sizeof(float4), hipHostMallocDefault));
+        }
+        rows = n_rows;
+    }
+}
+
+int set_render_uvs(const char *who, RenderTangents &T, const float *uv, int32_t count, int64_t rows, bool readback_pending) {
+    const std::string me(who);
+    if (readback_pending) return fail(SB_ERR_STATE, me + " while a readback is pending");
+    if (count == 0) { T.clear(); return SB_OK; }       // tangents off
+    if (rows < 0) return fail(SB_ERR_STATE, me + ": no render mode with triangles is set (sb_set_render_triangles, or sb_set_render_embedding with m_tri > 0, comes first)");
+    if (count < 0 || !uv) return fail(SB_ERR_INVALID_ARG, me + ": bad argument");
+    if (count != rows)
+        return fail(SB_ERR_INVALID_ARG, me + ": count is " + std::to_string(count) + ", the render mode in force has " + std::to_string(rows) + " vertices");
+    for (int64_t c = 0; c < 2 * (int64_t)count; ++c)
+        if (!std::isfinite(uv[c])) return fail(SB_ERR_INVALID_ARG, me + ": UV is NaN or infinite (vertex " + std::to_string(c / 2) + ")");
+    T.uv.assign(uv, uv + 2 * (size_t)count);
+    T.dirty = true;
     return SB_OK;
 }
 
@@ -285,9 +339,15 @@ static void begin_embedded(sb_solver *s, int k) {
     // ... normals (SPEC.md 6a on the skinned array) and D2H on the copy stream
     HIP_CHECK(hipStreamWaitEvent(s->copy_stream, s->ev_snap[k], 0));
     HIP_CHECK(hipMemcpyAsync(E.h_pos[k], E.d_pos[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
-    s->snap_has_normals[k] = false;
+    s->snap_has_normals[k] = false; s->tan.snap_has[k] = false;
     if (!E.tri.empty()) {
-        launch_normals(s->copy_stream, E.d_pos[k].p, E.d_adj_off.p, E.d_adj_tri.p, E.d_tri.p, E.d_nrm[k].p, (int)E.m, nullptr, nullptr);
+        if (s->tan.on()) {      // SPEC.md 6c: normals and tangents in one walk
+            s->tan.prepare(E.tri, (size_t)E.m, s->dev_bytes);
+            launch_normals_tangents(s->copy_stream, E.d_pos[k].p, E.d_adj_off.p, E.d_adj_tri.p, E.d_tri.p, s->tan.d_k.p, E.d_nrm[k].p, s->tan.d_tan[k].p, (int)E.m, nullptr, nullptr);
+            HIP_CHECK(hipMemcpyAsync(s->tan.h_tan[k], s->tan.d_tan[k].p, (size_t)E.m * sizeof(float4), hipMemcpyDeviceToHost, s->copy_stream));
+            s->tan.snap_has[k] = true;
+        } else
+            launch_normals(s->copy_stream, E.d_pos[k].p, E.d_adj_off.p, E.d_adj_tri.p, E.d_tri.p, E.d_nrm[k].p, (int)E.m, nullptr, nullptr);
         HIP_CHECK(hipMemcpyAsync(E.h_nrm[k], E.d_nrm[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
         s->snap_has_normals[k] = true;
     }
@@ -365,6 +425,8 @@ int sb_readback_begin(sb_solver *s) {
             s->render_dirty = false;
             s->n_peek_tiles = -1;
         }
+        const bool tangents = single && !s->render_tri.empty() && s->tan.on();
+        if (tangents) s->tan.prepare(s->render_tri, (size_t)s->n, s->dev_bytes);      // (sized like the normals: n rows, whatever a snapshot carries)
         sbk::PosView src = s->pos_view();
         // the tick's last kernel is deferred: snapshot a peek and leave it deferred
         src.xyz = const_cast<float *>(render_source(s, compact, s->render_local));
@@ -384,17 +446,24 @@ int sb_readback_begin(sb_solver *s) {
         HIP_CHECK(hipStreamWaitEvent(s->copy_stream, s->ev_snap[k], 0));
         if (!compact)
             HIP_CHECK(hipMemcpyAsync(s->h_snap[k], s->d_snap[k].p, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
-        s->snap_has_normals[k] = false;
+        s->snap_has_normals[k] = false; s->tan.snap_has[k] = false;
         s->snap_compact[k] = compact;
         s->snap_has_render_set[k] = !s->render_tri.empty();
         if (compact && !single && !s->render_set.empty())
             HIP_CHECK(hipMemcpyAsync(s->h_cpos[k], s->d_cpos[k].p, s->render_set.size() * 3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
         if (!s->render_tri.empty() && single) {
             const int count = compact ? (int)s->render_set.size() : (int)s->n;
-            hipLaunchKernelGGL(sbk::normals_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s->copy_stream, s->d_snap[k].p,
-                               s->d_adj_off.p, s->d_adj_tri.p, s->d_tri.p, s->d_nrm[k].p, count,
-                               compact ? s->d_render_set.p : (const int32_t *)nullptr, compact ? s->d_cpos[k].p : (float *)nullptr);
-            HIP_CHECK(hipGetLastError());
+            if (tangents) {     // SPEC.md 6c: normals and tangents in one walk
+                launch_normals_tangents(s->copy_stream, s->d_snap[k].p, s->d_adj_off.p, s->d_adj_tri.p, s->d_tri.p, s->tan.d_k.p, s->d_nrm[k].p, s->tan.d_tan[k].p, count,
+                                        compact ? s->d_render_set.p : (const int32_t *)nullptr, compact ? s->d_cpos[k].p : (float *)nullptr);
+                HIP_CHECK(hipMemcpyAsync(s->tan.h_tan[k], s->tan.d_tan[k].p, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost, s->copy_stream));
+                s->tan.snap_has[k] = true;
+            } else {
+                hipLaunchKernelGGL(sbk::normals_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s->copy_stream, s->d_snap[k].p,
+                                   s->d_adj_off.p, s->d_adj_tri.p, s->d_tri.p, s->d_nrm[k].p, count,
+                                   compact ? s->d_render_set.p : (const int32_t *)nullptr, compact ? s->d_cpos[k].p : (float *)nullptr);
+                HIP_CHECK(hipGetLastError());
+            }
             HIP_CHECK(hipMemcpyAsync(s->h_nrm[k], s->d_nrm[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
             if (compact)
                 HIP_CHECK(hipMemcpyAsync(s->h_cpos[k], s->d_cpos[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
@@ -430,6 +499,7 @@ int sb_set_render_triangles(sb_solver *s, const int32_t *tri, int32_t m) {
     return guarded([&]() -> int {
         for (int64_t c = 0; c < 3 * (int64_t)m; ++c)
             if (tri[c] < 0 || tri[c] >= s->n) return fail(SB_ERR_INVALID_ARG, "sb_set_render_triangles: particle index out of range");
+        s->tan.clear();         // every call that is accepted clears the UVs (sb_set_render_uvs): they belong to the triangle list they were given for
         s->render_tri.assign(tri, tri + 3 * (size_t)m);
         s->render_dirty = true;
         if (m == 0) s->render_set_only = false;
@@ -450,6 +520,7 @@ int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float 
         return fail(SB_ERR_STATE, "sb_set_render_embedding: render triangles are set (switch them off first: sb_set_render_triangles with m = 0)");
     return guarded([&]() -> int {
         if (int rc = check_embedding_args("sb_set_render_embedding", s->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri)) return rc;
+        s->tan.clear();         // every call that is accepted clears the UVs (sb_set_render_uvs)
         if (m_vertices == 0 && s->emb.m == 0) return SB_OK;      // off already
         std::vector<int32_t> cage(cage_ijkl, cage_ijkl + 4 * (size_t)m_vertices), tri(tri_abc, tri_abc + 3 * (size_t)m_tri);
         std::vector<float> w(weights4, weights4 + 4 * (size_t)m_vertices);
@@ -475,6 +546,29 @@ int sb_readback_get_normals(sb_solver *s, const float **out) {
     if (s->snap_last_ended < 0 || !s->snap_has_normals[s->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_readback_get_normals: no finished readback with render triangles set");
     *out = s->snap_embedded[s->snap_last_ended] ? s->emb.h_nrm[s->snap_last_ended] : s->h_nrm[s->snap_last_ended];
+    return SB_OK;
+}
+
+int sb_set_render_uvs(sb_solver *s, const float *uv, int32_t count) {
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_render_uvs: null handle");
+    if (s->desc.world > 1)
+        return fail(SB_ERR_UNSUPPORTED, "sb_set_render_uvs: a rank of a partitioned solver does not hold its neighbours' particles; vertex tangents of a partitioned "
+                    "body are computed on the gathered snapshot (sb_group_set_render_uvs)");
+    return guarded([&]() -> int {
+        if (s->finalized) { int rc = set_device(s); if (rc) return rc; }
+        const int64_t rows = !s->render_tri.empty() ? (int64_t)s->n : (s->emb.m > 0 && !s->emb.tri.empty() ? (int64_t)s->emb.m : -1);
+        return set_render_uvs("sb_set_render_uvs", s->tan, uv, count, rows, s->snap_pending != 0);
+    });
+}
+
+int sb_readback_get_tangents(sb_solver *s, const float **out) {
+    if (!s || !out) return fail(SB_ERR_INVALID_ARG, "sb_readback_get_tangents: null argument");
+    if (s->desc.world > 1)
+        return fail(SB_ERR_UNSUPPORTED, "sb_readback_get_tangents: a rank of a partitioned solver does not hold its neighbours' particles; vertex tangents of a partitioned "
+                    "body are computed on the gathered snapshot (sb_group_readback_get_tangents)");
+    if (s->snap_last_ended < 0 || !s->tan.snap_has[s->snap_last_ended])
+        return fail(SB_ERR_STATE, "sb_readback_get_tangents: no finished readback with render UVs set");
+    *out = reinterpret_cast<const float *>(s->tan.h_tan[s->snap_last_ended]);
     return SB_OK;
 }
 

@@ -1,5 +1,5 @@
 // readback_kernels.hip.hpp — render readback: snapshots in caller numbering, embedded render vertices (SPEC.md §6b) and area-weighted
-// vertex normals (SPEC.md §6a)
+// vertex normals (SPEC.md §6a), vertex tangents from UVs (SPEC.md §6c)
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 #pragma once
@@ -86,6 +86,60 @@ __global__ __launch_bounds__(256) void normals_kernel(const float *snap_xyz, con
         const size_t sv = 3 * (size_t)v;
         subset_pos_xyz[o] = snap_xyz[sv]; subset_pos_xyz[o + 1] = snap_xyz[sv + 1]; subset_pos_xyz[o + 2] = snap_xyz[sv + 2];
     }
+}
+
+// SPEC.md §6c: the normals of §6a and per-vertex tangents from UVs in one walk. Same lanes, same subset / compact convention and, for the
+// normal, the same statements as normals_kernel -- a readback delivers the same normal bits with and without UVs. The three corners of an
+// incident triangle are gathered once and feed the face normal and both tangent-frame sums (tri_k: the triangle's four UV coefficients,
+// one 16-byte load). A latency-bound gather: within an iteration the index, coefficient and corner loads do not depend on one another,
+// and the next triangle's id is fetched one iteration ahead of its use. The 12 accumulators and 9 corner coordinates leave the lane far
+// below the 64 registers full occupancy allows. No contraction (the unit is built with it off); tangent out as one 16-byte store.
+__global__ __launch_bounds__(256) void normals_tangents_kernel(const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri,
+                                                               const int32_t *tri, const float4 *tri_k, float *nrm_xyz, float4 *tan_xyzw,
+                                                               int n, const int32_t *subset, float *subset_pos_xyz) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const int v = subset ? subset[k] : k;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    V3 S = {0.0f, 0.0f, 0.0f}, T = {0.0f, 0.0f, 0.0f};
+    int q = adj_off[v];
+    const int q_end = adj_off[v + 1];
+    int t = q < q_end ? adj_tri[q] : 0;
+    for (; q < q_end; ++q) {
+        const int t_next = q + 1 < q_end ? adj_tri[q + 1] : t;
+        const size_t a = 3 * (size_t)tri[3 * t], b = 3 * (size_t)tri[3 * t + 1], c = 3 * (size_t)tri[3 * t + 2];
+        const float4 kk = tri_k[t];
+        const V3 xa = {snap_xyz[a], snap_xyz[a + 1], snap_xyz[a + 2]};
+        const V3 e1 = sub3({snap_xyz[b], snap_xyz[b + 1], snap_xyz[b + 2]}, xa);
+        const V3 e2 = sub3({snap_xyz[c], snap_xyz[c + 1], snap_xyz[c + 2]}, xa);
+        const V3 f = cross3(e1, e2);
+        nx = nx + f.x; ny = ny + f.y; nz = nz + f.z;
+        const V3 s = {kk.x * e1.x - kk.y * e2.x, kk.x * e1.y - kk.y * e2.y, kk.x * e1.z - kk.y * e2.z};
+        const V3 g = {kk.z * e2.x - kk.w * e1.x, kk.z * e2.y - kk.w * e1.y, kk.z * e2.z - kk.w * e1.z};
+        S.x = S.x + s.x; S.y = S.y + s.y; S.z = S.z + s.z;
+        T.x = T.x + g.x; T.y = T.y + g.y; T.z = T.z + g.z;
+        t = t_next;
+    }
+    float xx = nx * nx, yy = ny * ny, zz = nz * nz;
+    float L2 = (xx + yy) + zz;
+    if (L2 >= 0x1p-96f) { float L = sqrt_rn_normal(L2); nx = nx / L; ny = ny / L; nz = nz / L; }
+    else { nx = 0.0f; ny = 0.0f; nz = 0.0f; }
+    const size_t o = 3 * (size_t)k;
+    nrm_xyz[o] = nx; nrm_xyz[o + 1] = ny; nrm_xyz[o + 2] = nz;
+    if (subset) {
+        const size_t sv = 3 * (size_t)v;
+        subset_pos_xyz[o] = snap_xyz[sv]; subset_pos_xyz[o + 1] = snap_xyz[sv + 1]; subset_pos_xyz[o + 2] = snap_xyz[sv + 2];
+    }
+    // Gram-Schmidt against the normal, handedness from the accumulated bitangent
+    const V3 nn = {nx, ny, nz};
+    const float d = dot3(nn, S);
+    const float dx = d * nn.x, dy = d * nn.y, dz = d * nn.z;
+    V3 u = {S.x - dx, S.y - dy, S.z - dz};
+    const float U2 = dot3(u, u);
+    if (U2 >= 0x1p-96f) { float U = sqrt_rn_normal(U2); u.x = u.x / U; u.y = u.y / U; u.z = u.z / U; }
+    else { u.x = 0.0f; u.y = 0.0f; u.z = 0.0f; }
+    const float h = dot3(cross3(nn, S), T);
+    tan_xyzw[k] = make_float4(u.x, u.y, u.z, h < 0.0f ? -1.0f : 1.0f);
 }
 
 }  // namespace sbk

@@ -108,6 +108,38 @@ struct DevBuf {
     ~DevBuf() { free(); }
 };
 
+// Render tangents (sb_set_render_uvs, SPEC.md 6c) of a solver or of a group's render device: the UVs of the render mode in force, the
+// per-triangle coefficient table made from them, and per snapshot slot the tangents on the device and in pinned memory.
+struct RenderTangents {
+    static constexpr int kSlots = 3;       // (= kSnapSlots of the solver and of the group)
+    std::vector<float> uv;                 // 2 floats per vertex of the render mode in force; empty = tangents off
+    bool dirty = false;                    // UVs changed since the coefficient table was uploaded
+    DevBuf<float4> d_k;                    // (dv2, dv1, du1, du2) / det per triangle, zeros for a UV-degenerate one
+    DevBuf<float4> d_tan[kSlots];
+    float4 *h_tan[kSlots] = {nullptr, nullptr, nullptr};
+    size_t rows = 0;                       // capacity of every slot's buffers
+    bool snap_has[kSlots] = {false, false, false};
+    bool on() const { return !uv.empty(); }
+    void release() {                       // device and pinned buffers (no readback is pending when the UVs or the render mode change)
+        d_k.free();
+        for (int k = 0; k < kSlots; ++k) {
+            d_tan[k].free();
+            if (h_tan[k]) (void)hipHostFree(h_tan[k]);
+            h_tan[k] = nullptr;
+        }
+        rows = 0;
+    }
+    void clear() {                         // tangents off: what every sb_set_render_triangles / sb_set_render_embedding does
+        std::vector<float>().swap(uv);
+        dirty = false;
+        for (bool &b : snap_has) b = false;
+        release();
+    }
+    // before a readback that computes tangents: the coefficient table of `tri` (readback.hip) and buffers of at least n_rows rows
+    void prepare(const std::vector<int32_t> &tri, size_t n_rows, int64_t &acct);
+    ~RenderTangents() { release(); }
+};
+
 struct DevHalo {                 // one halo slot: who we talk to and which particles travel
     std::vector<int> peers;
     std::vector<int32_t> send_off, recv_off;  // per peer (+1), in particles
@@ -312,6 +344,7 @@ struct sb_solver {
         }
     } emb;
     bool snap_embedded[kSnapSlots] = {false, false, false};
+    sbi::RenderTangents tan;               // render tangents of either mode (sb_set_render_uvs): d_tan[q] / h_tan[q] / snap_has[q] per snapshot slot
     // kinematic targets (sb_set_kinematic_positions): a ring of pinned host tables the scatter kernel reads directly; a table is reused
     // only after the kernel that read it has finished (its event)
     static constexpr int kKinSlots = 4;
@@ -375,6 +408,7 @@ struct sb_solver {
             if (ev_copied[k]) (void)hipEventDestroy(ev_copied[k]);
         }
         emb.release();
+        tan.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (int k = 0; k < kKinSlots; ++k) {
             if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
@@ -430,7 +464,14 @@ void launch_snapshot_all(sb_solver *s, const float *src_xyz, const int32_t *d_ta
 void launch_snapshot_subset(sb_solver *s, const float *src_xyz, const int32_t *d_ids, const int32_t *d_local, int count, float *dst_xyz);
 void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, float *nrm_xyz, int count,
                     const int32_t *subset, float *subset_pos_xyz);
+// the same with tangents (SPEC.md 6c): tri_k = RenderTangents::d_k, tan_xyzw one float4 per lane
+void launch_normals_tangents(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, const float4 *tri_k,
+                             float *nrm_xyz, float4 *tan_xyzw, int count, const int32_t *subset, float *subset_pos_xyz);
 void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m);
+// sb_set_render_uvs / sb_group_set_render_uvs: the rules both share. rows = vertices of the triangle-bearing render mode in force (-1: none)
+int set_render_uvs(const char *who, RenderTangents &T, const float *uv, int32_t count, int64_t rows, bool readback_pending);
+// SPEC.md 6c, static part: (dv2, dv1, du1, du2) / det per triangle in f32, zeros where det == 0 or a quotient is not finite
+void tangent_coefficients(const std::vector<float> &uv, const std::vector<int32_t> &tri, std::vector<float4> &k);
 // sb_set_render_embedding / sb_group_set_render_embedding: the argument rules both share (n = particles the cage may name)
 int check_embedding_args(const char *who, int32_t n, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri);
 // incident-triangle lists per vertex, triangle ids ascending (what normals_kernel walks)

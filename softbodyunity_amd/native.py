@@ -129,6 +129,8 @@ SIGNATURES = {
     "sb_set_render_triangles": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "sb_set_render_embedding": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "sb_readback_get_normals": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
+    "sb_set_render_uvs": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
+    "sb_readback_get_tangents": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_set_readback_render_set_only": (C.c_int, [_P, C.c_int32]),
     "sb_readback_get_render_set": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
     "sb_get_owner": (C.c_int, [_P, _P, C.c_int32]),
@@ -184,10 +186,12 @@ SIGNATURES = {
     "sb_group_set_kinematic_positions": (C.c_int, [_P, _P, _P, C.c_int32]),
     "sb_group_set_render_triangles": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "sb_group_set_render_embedding": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "sb_group_set_render_uvs": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "sb_group_set_readback_render_set_only": (C.c_int, [_P, C.c_int32]),
     "sb_group_readback_begin": (C.c_int, [_P]),
     "sb_group_readback_end": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_group_readback_get_normals": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
+    "sb_group_readback_get_tangents": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_group_readback_get_render_set": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
     "sb_group_synchronize": (C.c_int, [_P]),
     "sb_group_rank_count": (C.c_int32, [_P]),

@@ -177,11 +177,12 @@ class Softbody:
     def readback_begin(self):
         check(native.lib().sb_readback_begin(self._h))
 
-    def readback_end(self, normals=False):
+    def readback_end(self, normals=False, tangents=False):
         """-> (N,3) float32 view of the plugin's pinned snapshot (valid until the second readback_begin after it);
         with normals=True -> (positions, vertex normals) -- needs set_render_triangles (SPEC.md 6a). In render-set-only
         mode both arrays are compact, (count,3), entry k belonging to particle render_set()[k]. With an embedding set
-        (set_render_embedding) both arrays are (m,3): the skinned render vertices and their normals, in the caller's vertex order."""
+        (set_render_embedding) both arrays are (m,3): the skinned render vertices and their normals, in the caller's vertex order.
+        With tangents=True -> (positions, normals, tangents), tangents (rows,4) = xyz + handedness -- needs set_render_uvs (SPEC.md 6c)."""
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_readback_end(self._h, C.byref(p)))
         rows = self.n
@@ -190,11 +191,16 @@ class Softbody:
         elif self._render_set_only:
             rows = len(self.render_set())
         pos = np.ctypeslib.as_array(p, shape=(rows, 3))
-        if not normals:
+        if not normals and not tangents:
             return pos
         q = C.POINTER(C.c_float)()
         check(native.lib().sb_readback_get_normals(self._h, C.byref(q)))
-        return pos, np.ctypeslib.as_array(q, shape=(rows, 3))
+        nrm = np.ctypeslib.as_array(q, shape=(rows, 3))
+        if not tangents:
+            return pos, nrm
+        t = C.POINTER(C.c_float)()
+        check(native.lib().sb_readback_get_tangents(self._h, C.byref(t)))
+        return pos, nrm, np.ctypeslib.as_array(t, shape=(rows, 4))
 
     def set_readback_render_set_only(self, on=True):
         """Readbacks bring only the particles the render triangles use (compact arrays)."""
@@ -219,6 +225,13 @@ class Softbody:
         cage, weights, tri, m = _embedding_args(cage, weights, tri)
         check(native.lib().sb_set_render_embedding(self._h, _ip(cage), _fp(weights), m, _ip(tri), 0 if tri is None else tri.shape[0]))
         self._embedded = m
+
+    def set_render_uvs(self, uv):
+        """Render tangents (SPEC.md 6c): one (u, v) pair per vertex of the render mode in force -- per particle with set_render_triangles,
+        per render vertex with set_render_embedding(..., tri). Every later readback also brings tangents (readback_end(tangents=True)).
+        uv=None switches them off, as does every set_render_triangles / set_render_embedding."""
+        uv, count = _uv_args(uv)
+        check(native.lib().sb_set_render_uvs(self._h, _fp(uv), count))
 
     def set_kinematic_positions(self, ids, pos):
         """Move pinned particles (inverse mass 0) to new positions between two ticks (SPEC.md 2, attachments)."""
@@ -292,6 +305,14 @@ def _embedding_args(cage, weights, tri):
     if tri is not None:
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
     return cage, weights, tri, cage.shape[0]
+
+
+def _uv_args(uv):
+    """-> (uv (count,2) float32 or None, count) as sb_set_render_uvs takes them"""
+    if uv is None:
+        return None, 0
+    uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    return uv, uv.shape[0]
 
 
 def _ip(a):
@@ -429,6 +450,11 @@ class SoftbodyGroup:
         check(native.lib().sb_group_set_render_embedding(self._g, _ip(cage), _fp(weights), m, _ip(tri), 0 if tri is None else tri.shape[0]))
         self._embedded = m
 
+    def set_render_uvs(self, uv):
+        """Softbody.set_render_uvs on the gathered snapshot: UVs per whole-mesh particle, or per render vertex of the embedding."""
+        uv, count = _uv_args(uv)
+        check(native.lib().sb_group_set_render_uvs(self._g, _fp(uv), count))
+
     def set_readback_render_set_only(self, on=True):
         check(native.lib().sb_group_set_readback_render_set_only(self._g, 1 if on else 0))
         self._render_set_only = bool(on)
@@ -441,16 +467,21 @@ class SoftbodyGroup:
         check(native.lib().sb_group_readback_get_render_set(self._g, C.byref(ids), C.byref(cnt)))
         return np.ctypeslib.as_array(ids, shape=(cnt.value,)) if cnt.value else np.zeros(0, np.int32)
 
-    def readback_end(self, normals=False):
+    def readback_end(self, normals=False, tangents=False):
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_group_readback_end(self._g, C.byref(p)))
         rows = self._embedded if self._embedded else (len(self.render_set()) if self._render_set_only else self.n)
         pos = np.ctypeslib.as_array(p, shape=(rows, 3))
-        if not normals:
+        if not normals and not tangents:
             return pos
         q = C.POINTER(C.c_float)()
         check(native.lib().sb_group_readback_get_normals(self._g, C.byref(q)))
-        return pos, np.ctypeslib.as_array(q, shape=(rows, 3))
+        nrm = np.ctypeslib.as_array(q, shape=(rows, 3))
+        if not tangents:
+            return pos, nrm
+        t = C.POINTER(C.c_float)()
+        check(native.lib().sb_group_readback_get_tangents(self._g, C.byref(t)))
+        return pos, nrm, np.ctypeslib.as_array(t, shape=(rows, 4))
 
     def _rank_handle(self, r):
         h = C.c_void_p()
