@@ -2,7 +2,7 @@
 //
 // Start()       -> sb_group_create + sb_group_set_particles/sb_group_set_*_constraints + sb_group_finalize   (plan, partition, upload)
 // FixedUpdate() -> sb_group_step(Time.fixedDeltaTime, substeps) + sb_group_get_positions                     (one tick, SPEC.md §2)
-//                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) instead (one tick of latency, no stall)
+//                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
 // OnDestroy()   -> sb_group_destroy
 //
 // A Unity player is ONE process: the component talks to the plugin through include/softbody_group.h, where `deviceCount` GPUs sit
@@ -75,6 +75,8 @@ namespace SoftbodyMI355X
         Mesh mesh;
         GCHandle posPin;
         Vector3[] normals;
+        readonly float[] boundsLo = new float[3], boundsHi = new float[3];      // the box of the snapshot shown (sb_group_readback_get_bounds)
+        bool haveBounds;
         Vector4[] tangents;                    // non-null: UVs were handed over (sb_group_set_render_uvs) and every readback brings tangents
         bool snapshotPending;
 
@@ -145,6 +147,8 @@ namespace SoftbodyMI355X
                 SoftbodyNative.Check(SoftbodyNative.sb_group_set_ground_plane(handle, groundNormal.x, groundNormal.y, groundNormal.z, groundOffset, 1), "sb_group_set_ground_plane");
             SoftbodyNative.Check(SoftbodyNative.sb_group_finalize(handle), "sb_group_finalize");
             posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
+            // the box of what a readback delivers, on the GPU (SPEC.md 6d), instead of Unity's scan of every vertex at each mesh.vertices assignment
+            if (asyncReadback) SoftbodyNative.Check(SoftbodyNative.sb_group_set_readback_bounds(handle, 1), "sb_group_set_readback_bounds");
             if (asyncReadback && visualMesh != null && volumeIJKL != null && volumeIJKL.Length >= 4)
             {
                 // embedded render mesh: bind every visual vertex to the tet that holds it in the rest pose, hand cage + weights + the visual
@@ -218,9 +222,21 @@ namespace SoftbodyMI355X
                         SoftbodyNative.Check(SoftbodyNative.sb_group_readback_get_tangents(handle, out IntPtr tan), "sb_group_readback_get_tangents");
                         CopyVectors4(tan, tangents);
                     }
+                    SoftbodyNative.Check(SoftbodyNative.sb_group_readback_get_bounds(handle, boundsLo, boundsHi), "sb_group_readback_get_bounds");
+                    haveBounds = true;
                 }
                 snapshotPending = true;
-                mesh.vertices = positions;
+                if (haveBounds)
+                {
+                    // no rescan on the main thread: the box came with the snapshot. An empty or non-finite box (no rows, NaN or infinite
+                    // positions) is not assigned: the mesh keeps the bounds it had
+                    mesh.SetVertices(positions, 0, positions.Length, UnityEngine.Rendering.MeshUpdateFlags.DontRecalculateBounds);
+                    var lo = new Vector3(boundsLo[0], boundsLo[1], boundsLo[2]);
+                    var hi = new Vector3(boundsHi[0], boundsHi[1], boundsHi[2]);
+                    if (IsFinite(lo) && IsFinite(hi) && lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z)
+                        mesh.bounds = new Bounds((lo + hi) * 0.5f, hi - lo);
+                }
+                else mesh.vertices = positions;              // (the first tick: nothing has been read back yet)
                 if (normals != null) mesh.normals = normals; else mesh.RecalculateNormals();
                 if (tangents != null) mesh.tangents = tangents;
                 return;
@@ -236,6 +252,11 @@ namespace SoftbodyMI355X
             }
             mesh.vertices = positions;
             mesh.RecalculateNormals();
+        }
+
+        static bool IsFinite(Vector3 v)
+        {
+            return !(float.IsNaN(v.x) || float.IsInfinity(v.x) || float.IsNaN(v.y) || float.IsInfinity(v.y) || float.IsNaN(v.z) || float.IsInfinity(v.z));
         }
 
         void OnDestroy()

@@ -163,6 +163,10 @@ namespace SoftbodyMI355X
         // render tangents (SPEC.md 6c): uv = 2 floats per vertex of the render mode in force (a pinned Vector2[]); tangents = Vector4 per row (xyz, handedness)
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_uvs(IntPtr s, IntPtr uv, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_tangents(IntPtr s, out IntPtr tangentXyzw);
+        // bounding box (SPEC.md 6d): lo / hi are float[3], filled by the call
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_bounds(IntPtr s, int enabled);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_bounds(IntPtr s, [Out] float[] loXyz, [Out] float[] hiXyz);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_get_bounds(IntPtr s, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_render_set_only(IntPtr s, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_render_set(IntPtr s, out IntPtr ids, out int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_get_owner(IntPtr s, IntPtr ownerRankOut, int n);
@@ -223,6 +227,9 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_normals(IntPtr g, out IntPtr normalXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_tangents(IntPtr g, out IntPtr tangentXyzw);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_render_set(IntPtr g, out IntPtr ids, out int count);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_readback_bounds(IntPtr g, int enabled);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_rank_count(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_rank(IntPtr g, int rank, out IntPtr solver);

@@ -21,7 +21,7 @@
  *    SB_ERR_NO_DEVICE.
  *  - Semantics of one tick: SPEC.md.
  *
- * This header is the whole PRODUCT surface of a solver handle (35 functions). Beside it:
+ * This header is the whole PRODUCT surface of a solver handle (38 functions). Beside it:
  *   softbody_group.h  one process -- a Unity player -- driving several GPUs behind the same component (sb_group_*)
  *   softbody_plan.h   host-only planner inspection (published order, tiles, halo lists; frame / window of sharded authoring)
  *   softbody_debug.h  test hooks, the table validator, per-launch timing and the tuning switches of A/B measurements
@@ -254,6 +254,24 @@ int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float 
  * vertices may be duplicated freely. */
 int sb_set_render_uvs(sb_solver *s, const float *uv /* 2 floats per vertex */, int32_t count);
 int sb_readback_get_tangents(sb_solver *s, const float **tangent_xyzw_out);
+/* Bounding box (SPEC.md 6d; replaces the scan of every vertex Unity runs on the main thread when mesh.vertices is assigned without bounds):
+ * lo / hi = the component-wise minimum / maximum of a set of rows, exact, NaN components ignored, +inf / -inf where a component has no value
+ * (no rows, or NaN only: the "empty box"), a zero result always +0. Two small kernels and 32 bytes to the host; no atomics.
+ *  - sb_set_readback_bounds(enabled != 0): every later sb_readback_begin also reduces the array THAT snapshot delivers -- all n particles; on a
+ *    rank of a partitioned solver (world > 1) the particles it owns (the zero entries of other ranks' particles take no part); with
+ *    render_set_only the render set's rows (a rank: the render particles it owns); with an embedding the m_vertices skinned vertices -- on the
+ *    copy stream, behind the kernel that produces the array. Off by default: a readback then enqueues exactly what it did without this call.
+ *    Before or after sb_finalize; SB_ERR_STATE while a readback is pending (nothing is changed). The setting belongs to no triangle list:
+ *    sb_set_render_triangles, sb_set_render_embedding and sb_set_render_uvs leave it alone.
+ *  - sb_readback_get_bounds, after the matching sb_readback_end: copies the six floats of the snapshot ended last (nothing to keep alive).
+ *    SB_ERR_STATE when that snapshot was begun with bounds off (switching them on afterwards does not help) or no readback has ended;
+ *    SB_ERR_INVALID_ARG on a null argument. Works on a rank of a partitioned solver: boxes compose by min / max, so a host may combine them.
+ *  - sb_get_bounds: synchronous like sb_get_positions, and on the same data -- the box of every particle this rank owns as sb_get_positions
+ *    would return it now: it PEEKS where that peeks (sb_stats.readback_peeks rises, the tick stays fusable, pending kinematic targets show)
+ *    and completes the tick where that does. 32 bytes cross to the host instead of the state. SB_ERR_STATE before sb_finalize. */
+int sb_set_readback_bounds(sb_solver *s, int32_t enabled);
+int sb_readback_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]);
+int sb_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]);
 int sb_get_owner(sb_solver *s, int32_t *owner_rank_out, int32_t n);
 
 

@@ -109,6 +109,13 @@ int sb_group_readback_end(sb_group *g, const float **pos_xyz_out);
 int sb_group_readback_get_normals(sb_group *g, const float **normal_xyz_out);
 int sb_group_readback_get_tangents(sb_group *g, const float **tangent_xyzw_out);
 int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids_out, int32_t *count_out);
+/* Bounding box (sb_set_readback_bounds / sb_readback_get_bounds / sb_get_bounds, SPEC.md 6d), same contract. The readback box is computed on the
+ * render device on the array the group delivers -- the gathered snapshot, the compact render set or the skinned vertices -- after the gather.
+ * sb_group_get_bounds asks every rank for the box of what it owns (each peeks or completes its tick as sb_group_get_positions would make it; 32
+ * bytes per rank) in both host models and combines the answers on the host: component-wise min / max, then + 0.0f. */
+int sb_group_set_readback_bounds(sb_group *g, int32_t enabled);
+int sb_group_readback_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
+int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
 
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);

@@ -126,6 +126,7 @@ struct sb_group {
     float *h_emb_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_emb_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
     bool snap_embedded[kSnapSlots] = {false, false, false};
     RenderTangents tan;                          // render tangents of either mode (sb_group_set_render_uvs, SPEC.md 6c), on the render device
+    ReadbackBounds bnd;                          // bounding box of the delivered array (sb_group_set_readback_bounds, SPEC.md 6d), on the render device
     void release_embedding() {                   // on the render device; no readback is pending when the embedding changes
         d_emb_cage.free(); d_emb_w.free(); d_emb_tri.free(); d_emb_adj_off.free(); d_emb_adj_tri.free();
         for (int k = 0; k < kSnapSlots; ++k) {
@@ -170,6 +171,7 @@ struct sb_group {
         d_tri.free(); d_adj_off.free(); d_adj_tri.free(); d_render_set.free();
         release_embedding();
         tan.release();
+        bnd.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (size_t r = 0; r < rr.size(); ++r) {
             (void)hipSetDevice(devices[r]);
@@ -859,6 +861,8 @@ int sb_group_readback_begin(sb_group *g) {
                 g->snap_has_normals[k] = true;
             }
             g->snap_compact[k] = false; g->snap_embedded[k] = true;
+            g->bnd.snap_has[k] = g->bnd.enabled;
+            if (g->bnd.enabled) launch_bounds(g->copy_stream, g->bnd, k, g->d_emb_pos[k].p, nullptr, g->emb_m, g->dev_bytes);      // SPEC.md 6d on the skinned vertices
             HIP_CHECK(hipEventRecord(g->ev_copied[k], g->copy_stream));
             ++g->snap_pending;
             return SB_OK;
@@ -920,6 +924,11 @@ int sb_group_readback_begin(sb_group *g) {
             if (compact) HIP_CHECK(hipMemcpyAsync(g->h_cpos[k], g->d_cpos[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
             g->snap_has_normals[k] = true;
         }
+        g->bnd.snap_has[k] = g->bnd.enabled;
+        if (g->bnd.enabled) {       // SPEC.md 6d on the delivered array: every rank's rows are in the gather buffer by now
+            if (compact) launch_bounds(g->copy_stream, g->bnd, k, g->d_cpos[k].p, nullptr, (int64_t)g->render_set.size(), g->dev_bytes);
+            else launch_bounds(g->copy_stream, g->bnd, k, g->d_gather[k].p, nullptr, (int64_t)g->n, g->dev_bytes);
+        }
         HIP_CHECK(hipEventRecord(g->ev_copied[k], g->copy_stream));
         ++g->snap_pending;
         return SB_OK;
@@ -954,6 +963,39 @@ int sb_group_readback_get_tangents(sb_group *g, const float **out) {
     if (g->snap_last_ended < 0 || !g->tan.snap_has[g->snap_last_ended])
         return fail(SB_ERR_STATE, "sb_group_readback_get_tangents: no finished readback with render UVs set");
     *out = reinterpret_cast<const float *>(g->tan.h_tan[g->snap_last_ended]);
+    return SB_OK;
+}
+
+int sb_group_set_readback_bounds(sb_group *g, int32_t enabled) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_readback_bounds: null group");
+    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_readback_bounds while a readback is pending");
+    g->bnd.enabled = enabled != 0;
+    return SB_OK;
+}
+
+int sb_group_readback_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
+    if (!g || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_bounds: null argument");
+    if (g->snap_last_ended < 0 || !g->bnd.snap_has[g->snap_last_ended])
+        return fail(SB_ERR_STATE, "sb_group_readback_get_bounds: no finished readback that was begun with bounds on (sb_group_set_readback_bounds)");
+    g->bnd.read(g->snap_last_ended, lo_xyz, hi_xyz);
+    return SB_OK;
+}
+
+int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
+    if (!g || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_group_get_bounds: null argument");
+    if (int rc = check_group(g, true, "sb_group_get_bounds")) return rc;
+    // every rank reduces what it owns on its own device (32 bytes each to the host); min and max compose exactly (SPEC.md 6d)
+    std::vector<std::array<float, 6>> box((size_t)g->W);
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return get_bounds_owned(g->ranks[(size_t)r], &box[(size_t)r][0], &box[(size_t)r][3]); }); });
+    if (rc) return rc;
+    for (int c = 0; c < 3; ++c) {
+        float lo = std::numeric_limits<float>::infinity(), hi = -lo;
+        for (int r = 0; r < g->W; ++r) {
+            if (box[(size_t)r][(size_t)c] < lo) lo = box[(size_t)r][(size_t)c];
+            if (box[(size_t)r][(size_t)c + 3] > hi) hi = box[(size_t)r][(size_t)c + 3];
+        }
+        lo_xyz[c] = lo + 0.0f; hi_xyz[c] = hi + 0.0f;
+    }
     return SB_OK;
 }
 

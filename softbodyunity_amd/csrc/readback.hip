@@ -1,4 +1,4 @@
-// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals, tangents and embedded render vertices
+// readback.hip — state reads and writes, kinematic targets, the asynchronous render readback with GPU vertex normals, tangents, embedded render vertices and the bounding box
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
@@ -133,6 +133,35 @@ void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const f
     if (m <= 0) return;
     hipLaunchKernelGGL(sbk::skin_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src_xyz, cage, weights, out_xyz, m);
     HIP_CHECK(hipGetLastError());
+}
+
+void ReadbackBounds::prepare(int64_t &acct) {
+    if (h_box) return;
+    d_partials.alloc((size_t)2 * 6 * sbk::kBoundsMaxGroups, acct);
+    d_box.alloc((size_t)8 * (kSlots + 1), acct);
+    HIP_CHECK(hipHostMalloc((void **)&h_box, (size_t)8 * (kSlots + 1) * sizeof(float), hipHostMallocDefault));
+}
+
+void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz, const int32_t *rows, int64_t count, int64_t &acct) {
+    B.prepare(acct);
+    float *partials = B.d_partials.p + (slot == ReadbackBounds::kQuerySlot ? (size_t)6 * sbk::kBoundsMaxGroups : 0);
+    const int groups = (int)std::min<int64_t>((count + sbk::kBoundsLanes - 1) / sbk::kBoundsLanes, sbk::kBoundsMaxGroups);
+    if (groups) hipLaunchKernelGGL(sbk::bounds_partial_kernel, dim3((unsigned)groups), dim3(sbk::kBoundsLanes), 0, st, xyz, rows, (int)count, partials);
+    hipLaunchKernelGGL(sbk::bounds_final_kernel, dim3(1), dim3(sbk::kBoundsLanes), 0, st, partials, groups, B.d_box.p + 8 * (size_t)slot);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(B.h_box + 8 * (size_t)slot, B.d_box.p + 8 * (size_t)slot, 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+}
+
+int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]) {
+    int rc = set_device(s); if (rc) return rc;
+    const bool peek = can_peek(s);
+    if (peek) { peek_positions(s, false); if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p); }     // (as get_state_owned reads positions)
+    else flush_deferred(s);
+    launch_bounds(s->stream, s->bnd, ReadbackBounds::kQuerySlot, peek ? s->d_peek.p : s->d_pos3.p, nullptr, s->n_owned, s->dev_bytes);
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    check_peer_error(s);
+    s->bnd.read(ReadbackBounds::kQuerySlot, lo, hi);
+    return SB_OK;
 }
 
 int check_embedding_args(const char *who, int32_t n, const int32_t *cage, const float *w, int32_t m, const int32_t *tri, int32_t m_tri) {
@@ -352,6 +381,8 @@ static void begin_embedded(sb_solver *s, int k) {
         s->snap_has_normals[k] = true;
     }
     s->snap_compact[k] = false; s->snap_has_render_set[k] = false; s->snap_embedded[k] = true;
+    s->bnd.snap_has[k] = s->bnd.enabled;
+    if (s->bnd.enabled) launch_bounds(s->copy_stream, s->bnd, k, E.d_pos[k].p, nullptr, E.m, s->dev_bytes);      // SPEC.md 6d on the skinned vertices
     HIP_CHECK(hipEventRecord(s->ev_copied[k], s->copy_stream));
     ++s->snap_pending;
 }
@@ -469,6 +500,11 @@ int sb_readback_begin(sb_solver *s) {
                 HIP_CHECK(hipMemcpyAsync(s->h_cpos[k], s->d_cpos[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
             s->snap_has_normals[k] = true;
         }
+        s->bnd.snap_has[k] = s->bnd.enabled;
+        if (s->bnd.enabled) {       // SPEC.md 6d on what this snapshot delivers: the compact array, or the rows of the full one this rank owns
+            if (compact) launch_bounds(s->copy_stream, s->bnd, k, s->d_cpos[k].p, nullptr, (int64_t)s->render_set.size(), s->dev_bytes);
+            else launch_bounds(s->copy_stream, s->bnd, k, s->d_snap[k].p, single ? (const int32_t *)nullptr : s->d_local_to_old.p, single ? (int64_t)s->n : s->n_owned, s->dev_bytes);
+        }
         HIP_CHECK(hipEventRecord(s->ev_copied[k], s->copy_stream));
         ++s->snap_pending;
         return SB_OK;
@@ -570,6 +606,27 @@ int sb_readback_get_tangents(sb_solver *s, const float **out) {
         return fail(SB_ERR_STATE, "sb_readback_get_tangents: no finished readback with render UVs set");
     *out = reinterpret_cast<const float *>(s->tan.h_tan[s->snap_last_ended]);
     return SB_OK;
+}
+
+int sb_set_readback_bounds(sb_solver *s, int32_t enabled) {
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_readback_bounds: null handle");
+    if (s->snap_pending) return fail(SB_ERR_STATE, "sb_set_readback_bounds while a readback is pending");
+    s->bnd.enabled = enabled != 0;
+    return SB_OK;
+}
+
+int sb_readback_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]) {
+    if (!s || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_readback_get_bounds: null argument");
+    if (s->snap_last_ended < 0 || !s->bnd.snap_has[s->snap_last_ended])
+        return fail(SB_ERR_STATE, "sb_readback_get_bounds: no finished readback that was begun with bounds on (sb_set_readback_bounds)");
+    s->bnd.read(s->snap_last_ended, lo_xyz, hi_xyz);
+    return SB_OK;
+}
+
+int sb_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]) {
+    if (!s || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_get_bounds: null argument");
+    if (!s->finalized) return fail(SB_ERR_STATE, "sb_get_bounds before sb_finalize");
+    return guarded([&]() -> int { return get_bounds_owned(s, lo_xyz, hi_xyz); });
 }
 
 int sb_set_readback_render_set_only(sb_solver *s, int32_t on) {

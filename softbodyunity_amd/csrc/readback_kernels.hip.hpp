@@ -142,4 +142,76 @@ __global__ __launch_bounds__(256) void normals_tangents_kernel(const float *snap
     tan_xyzw[k] = make_float4(u.x, u.y, u.z, h < 0.0f ? -1.0f : 1.0f);
 }
 
+// SPEC.md §6d: the axis-aligned box of a set of rows, in two launches and without atomics. Minimum and maximum are exact, and after the final
+// + 0.0f the box depends on the multiset of values only, so any tree gives the spec's bits. A NaN never wins a comparison: the accumulators
+// start at +inf / -inf and only ever take a value that compared less / greater, so no accumulator holds a NaN and the tree needs no NaN rule.
+constexpr int kBoundsLanes = 256;
+constexpr int kBoundsMaxGroups = 2048;      // grid cap of bounds_partial_kernel: 8 waves per SIMD on 256 CUs; larger sets walk the grid-stride loop
+
+struct Box6 { float lo[3], hi[3]; };
+
+__device__ __forceinline__ void box_take(Box6 &b, float x, float y, float z) {
+    if (x < b.lo[0]) b.lo[0] = x;
+    if (y < b.lo[1]) b.lo[1] = y;
+    if (z < b.lo[2]) b.lo[2] = z;
+    if (x > b.hi[0]) b.hi[0] = x;
+    if (y > b.hi[1]) b.hi[1] = y;
+    if (z > b.hi[2]) b.hi[2] = z;
+}
+// lo against lo, hi against hi: an empty component (+inf, -inf) must not leak its +inf into hi
+__device__ __forceinline__ void box_merge(Box6 &b, const float *lo_hi6) {
+    for (int c = 0; c < 3; ++c) {
+        if (lo_hi6[c] < b.lo[c]) b.lo[c] = lo_hi6[c];
+        if (lo_hi6[3 + c] > b.hi[c]) b.hi[c] = lo_hi6[3 + c];
+    }
+}
+
+// The workgroup's box in lane 0: a wave64 butterfly, then the four waves' boxes through LDS. Every lane of the 256 calls it.
+__device__ __forceinline__ void box_reduce_workgroup(Box6 &b) {
+    __shared__ float wave_box[kBoundsLanes / 64][6];
+    for (int m = 32; m >= 1; m >>= 1)
+        for (int c = 0; c < 3; ++c) {
+            const float l = __shfl_xor(b.lo[c], m, 64), h = __shfl_xor(b.hi[c], m, 64);
+            if (l < b.lo[c]) b.lo[c] = l;
+            if (h > b.hi[c]) b.hi[c] = h;
+        }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int c = 0; c < 3; ++c) { wave_box[wave][c] = b.lo[c]; wave_box[wave][3 + c] = b.hi[c]; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < kBoundsLanes / 64; ++w) box_merge(b, wave_box[w]);
+}
+
+// Lane k of the grid reduces rows k, k + grid, ... of a packed xyz array: row rows[k] where a row list is given (a rank's full snapshot:
+// the caller ids of the particles it owns), else row k -- neighbouring lanes then read neighbouring 12-byte rows, one 768-byte run per wave.
+// Workgroup g writes partials[6g .. 6g+5] = lo.xyz, hi.xyz. The launch has min(ceil(count / 256), kBoundsMaxGroups) workgroups.
+__global__ __launch_bounds__(kBoundsLanes) void bounds_partial_kernel(const float *xyz, const int32_t *rows, int count, float *partials) {
+    const float inf = __builtin_inff();
+    Box6 b = {{inf, inf, inf}, {-inf, -inf, -inf}};
+    const int stride = (int)gridDim.x * kBoundsLanes;
+    for (int64_t k = (int64_t)blockIdx.x * kBoundsLanes + threadIdx.x; k < count; k += stride) {
+        const size_t o = 3 * (size_t)(rows ? rows[k] : (int32_t)k);
+        box_take(b, xyz[o], xyz[o + 1], xyz[o + 2]);
+    }
+    box_reduce_workgroup(b);
+    if (threadIdx.x == 0) {
+        float *out = partials + 6 * (size_t)blockIdx.x;
+        out[0] = b.lo[0]; out[1] = b.lo[1]; out[2] = b.lo[2]; out[3] = b.hi[0]; out[4] = b.hi[1]; out[5] = b.hi[2];
+    }
+}
+
+// One workgroup reduces the n_partials rows of six floats (0 rows: the empty box), applies the + 0.0f that makes a zero result +0, and
+// writes box8 = lo.xyz, 0, hi.xyz, 0.
+__global__ __launch_bounds__(kBoundsLanes) void bounds_final_kernel(const float *partials, int n_partials, float *box8) {
+    const float inf = __builtin_inff();
+    Box6 b = {{inf, inf, inf}, {-inf, -inf, -inf}};
+    for (int g = threadIdx.x; g < n_partials; g += kBoundsLanes) box_merge(b, partials + 6 * (size_t)g);
+    box_reduce_workgroup(b);
+    if (threadIdx.x == 0) {
+        box8[0] = b.lo[0] + 0.0f; box8[1] = b.lo[1] + 0.0f; box8[2] = b.lo[2] + 0.0f; box8[3] = 0.0f;
+        box8[4] = b.hi[0] + 0.0f; box8[5] = b.hi[1] + 0.0f; box8[6] = b.hi[2] + 0.0f; box8[7] = 0.0f;
+    }
+}
+
 }  // namespace sbk

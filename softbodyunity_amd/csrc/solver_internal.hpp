@@ -140,6 +140,26 @@ struct RenderTangents {
     ~RenderTangents() { release(); }
 };
 
+// Bounding box (sb_set_readback_bounds / sb_get_bounds, SPEC.md 6d) of a solver or of a group's render device: per snapshot slot -- and once
+// more for the synchronous query, which runs on another stream -- the box on the device and in pinned memory, 8 floats: lo.xyz, 0, hi.xyz, 0.
+struct ReadbackBounds {
+    static constexpr int kSlots = 3;       // (= kSnapSlots of the solver and of the group)
+    static constexpr int kQuerySlot = kSlots;
+    bool enabled = false;                  // readbacks begun from now on carry a box
+    DevBuf<float> d_partials;              // the workgroups' boxes: one set for the copy stream, one for the query
+    DevBuf<float> d_box;                   // 8 floats per slot
+    float *h_box = nullptr;
+    bool snap_has[kSlots] = {false, false, false};
+    void prepare(int64_t &acct);           // buffers, at first use (readback.hip)
+    void read(int slot, float lo[3], float hi[3]) const { for (int c = 0; c < 3; ++c) { lo[c] = h_box[8 * slot + c]; hi[c] = h_box[8 * slot + 4 + c]; } }
+    void release() {
+        d_partials.free(); d_box.free();
+        if (h_box) (void)hipHostFree(h_box);
+        h_box = nullptr;
+    }
+    ~ReadbackBounds() { release(); }
+};
+
 struct DevHalo {                 // one halo slot: who we talk to and which particles travel
     std::vector<int> peers;
     std::vector<int32_t> send_off, recv_off;  // per peer (+1), in particles
@@ -345,6 +365,7 @@ struct sb_solver {
     } emb;
     bool snap_embedded[kSnapSlots] = {false, false, false};
     sbi::RenderTangents tan;               // render tangents of either mode (sb_set_render_uvs): d_tan[q] / h_tan[q] / snap_has[q] per snapshot slot
+    sbi::ReadbackBounds bnd;               // bounding box of the readbacks (sb_set_readback_bounds) and of sb_get_bounds
     // kinematic targets (sb_set_kinematic_positions): a ring of pinned host tables the scatter kernel reads directly; a table is reused
     // only after the kernel that read it has finished (its event)
     static constexpr int kKinSlots = 4;
@@ -409,6 +430,7 @@ struct sb_solver {
         }
         emb.release();
         tan.release();
+        bnd.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (int k = 0; k < kKinSlots; ++k) {
             if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
@@ -468,6 +490,11 @@ void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_of
 void launch_normals_tangents(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, const float4 *tri_k,
                              float *nrm_xyz, float4 *tan_xyzw, int count, const int32_t *subset, float *subset_pos_xyz);
 void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m);
+// SPEC.md 6d on stream st: the box of rows rows[0 .. count) (rows == nullptr: 0 .. count) of a packed xyz array -> the slot's 8 floats on the
+// device, then 32 bytes to the slot's pinned memory. count == 0 gives the empty box.
+void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz, const int32_t *rows, int64_t count, int64_t &acct);
+// sb_get_bounds: the box of the particles this rank owns, on what sb_get_positions would return now (peeks where that peeks)
+int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]);
 // sb_set_render_uvs / sb_group_set_render_uvs: the rules both share. rows = vertices of the triangle-bearing render mode in force (-1: none)
 int set_render_uvs(const char *who, RenderTangents &T, const float *uv, int32_t count, int64_t rows, bool readback_pending);
 // SPEC.md 6c, static part: (dv2, dv1, du1, du2) / det per triangle in f32, zeros where det == 0 or a quotient is not finite

@@ -131,6 +131,9 @@ SIGNATURES = {
     "sb_readback_get_normals": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_set_render_uvs": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "sb_readback_get_tangents": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
+    "sb_set_readback_bounds": (C.c_int, [_P, C.c_int32]),
+    "sb_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sb_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_set_readback_render_set_only": (C.c_int, [_P, C.c_int32]),
     "sb_readback_get_render_set": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
     "sb_get_owner": (C.c_int, [_P, _P, C.c_int32]),
@@ -193,6 +196,9 @@ SIGNATURES = {
     "sb_group_readback_get_normals": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_group_readback_get_tangents": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_group_readback_get_render_set": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
+    "sb_group_set_readback_bounds": (C.c_int, [_P, C.c_int32]),
+    "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_synchronize": (C.c_int, [_P]),
     "sb_group_rank_count": (C.c_int32, [_P]),
     "sb_group_get_rank": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

@@ -177,12 +177,14 @@ class Softbody:
     def readback_begin(self):
         check(native.lib().sb_readback_begin(self._h))
 
-    def readback_end(self, normals=False, tangents=False):
+    def readback_end(self, normals=False, tangents=False, bounds=False):
         """-> (N,3) float32 view of the plugin's pinned snapshot (valid until the second readback_begin after it);
         with normals=True -> (positions, vertex normals) -- needs set_render_triangles (SPEC.md 6a). In render-set-only
         mode both arrays are compact, (count,3), entry k belonging to particle render_set()[k]. With an embedding set
         (set_render_embedding) both arrays are (m,3): the skinned render vertices and their normals, in the caller's vertex order.
-        With tangents=True -> (positions, normals, tangents), tangents (rows,4) = xyz + handedness -- needs set_render_uvs (SPEC.md 6c)."""
+        With tangents=True -> (positions, normals, tangents), tangents (rows,4) = xyz + handedness -- needs set_render_uvs (SPEC.md 6c).
+        With bounds=True the tuple ends with (lo, hi), two float32 (3,) copies: the box of the delivered array -- needs set_readback_bounds
+        before the readback_begin (SPEC.md 6d)."""
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_readback_end(self._h, C.byref(p)))
         rows = self.n
@@ -190,17 +192,26 @@ class Softbody:
             rows = self._embedded
         elif self._render_set_only:
             rows = len(self.render_set())
-        pos = np.ctypeslib.as_array(p, shape=(rows, 3))
-        if not normals and not tangents:
-            return pos
-        q = C.POINTER(C.c_float)()
-        check(native.lib().sb_readback_get_normals(self._h, C.byref(q)))
-        nrm = np.ctypeslib.as_array(q, shape=(rows, 3))
-        if not tangents:
-            return pos, nrm
-        t = C.POINTER(C.c_float)()
-        check(native.lib().sb_readback_get_tangents(self._h, C.byref(t)))
-        return pos, nrm, np.ctypeslib.as_array(t, shape=(rows, 4))
+        out = [np.ctypeslib.as_array(p, shape=(rows, 3))]
+        if normals or tangents:
+            q = C.POINTER(C.c_float)()
+            check(native.lib().sb_readback_get_normals(self._h, C.byref(q)))
+            out.append(np.ctypeslib.as_array(q, shape=(rows, 3)))
+        if tangents:
+            t = C.POINTER(C.c_float)()
+            check(native.lib().sb_readback_get_tangents(self._h, C.byref(t)))
+            out.append(np.ctypeslib.as_array(t, shape=(rows, 4)))
+        if bounds:
+            out.append(_box(native.lib().sb_readback_get_bounds, self._h))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def set_readback_bounds(self, on=True):
+        """Readbacks begun from now on also bring the bounding box of what they deliver (readback_end(bounds=True), SPEC.md 6d)."""
+        check(native.lib().sb_set_readback_bounds(self._h, 1 if on else 0))
+
+    def get_bounds(self):
+        """-> (lo, hi), float32 (3,): the box of the particles this rank owns, on what get_positions() would return now (SPEC.md 6d)."""
+        return _box(native.lib().sb_get_bounds, self._h)
 
     def set_readback_render_set_only(self, on=True):
         """Readbacks bring only the particles the render triangles use (compact arrays)."""
@@ -305,6 +316,13 @@ def _embedding_args(cage, weights, tri):
     if tri is not None:
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
     return cage, weights, tri, cage.shape[0]
+
+
+def _box(fn, handle):
+    """(lo, hi) of one of the *_get_bounds entry points"""
+    lo = np.zeros(3, np.float32); hi = np.zeros(3, np.float32)
+    check(fn(handle, _fp(lo), _fp(hi)))
+    return lo, hi
 
 
 def _uv_args(uv):
@@ -467,21 +485,30 @@ class SoftbodyGroup:
         check(native.lib().sb_group_readback_get_render_set(self._g, C.byref(ids), C.byref(cnt)))
         return np.ctypeslib.as_array(ids, shape=(cnt.value,)) if cnt.value else np.zeros(0, np.int32)
 
-    def readback_end(self, normals=False, tangents=False):
+    def readback_end(self, normals=False, tangents=False, bounds=False):
         p = C.POINTER(C.c_float)()
         check(native.lib().sb_group_readback_end(self._g, C.byref(p)))
         rows = self._embedded if self._embedded else (len(self.render_set()) if self._render_set_only else self.n)
-        pos = np.ctypeslib.as_array(p, shape=(rows, 3))
-        if not normals and not tangents:
-            return pos
-        q = C.POINTER(C.c_float)()
-        check(native.lib().sb_group_readback_get_normals(self._g, C.byref(q)))
-        nrm = np.ctypeslib.as_array(q, shape=(rows, 3))
-        if not tangents:
-            return pos, nrm
-        t = C.POINTER(C.c_float)()
-        check(native.lib().sb_group_readback_get_tangents(self._g, C.byref(t)))
-        return pos, nrm, np.ctypeslib.as_array(t, shape=(rows, 4))
+        out = [np.ctypeslib.as_array(p, shape=(rows, 3))]
+        if normals or tangents:
+            q = C.POINTER(C.c_float)()
+            check(native.lib().sb_group_readback_get_normals(self._g, C.byref(q)))
+            out.append(np.ctypeslib.as_array(q, shape=(rows, 3)))
+        if tangents:
+            t = C.POINTER(C.c_float)()
+            check(native.lib().sb_group_readback_get_tangents(self._g, C.byref(t)))
+            out.append(np.ctypeslib.as_array(t, shape=(rows, 4)))
+        if bounds:
+            out.append(_box(native.lib().sb_group_readback_get_bounds, self._g))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def set_readback_bounds(self, on=True):
+        """Softbody.set_readback_bounds on the array the group delivers."""
+        check(native.lib().sb_group_set_readback_bounds(self._g, 1 if on else 0))
+
+    def get_bounds(self):
+        """-> (lo, hi): every rank's box of what it owns, combined on the host."""
+        return _box(native.lib().sb_group_get_bounds, self._g)
 
     def _rank_handle(self, r):
         h = C.c_void_p()
