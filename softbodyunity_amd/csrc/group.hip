@@ -5,7 +5,8 @@
 //
 // A group is N ordinary solvers (sb_desc.rank = r, world = N, device = devices[r]) plus what a single host needs around them: the whole
 // mesh authored once (cut into windows here when the partition is the block grid), the transport connected inside the process, one
-// call per tick, state gathered in the caller's numbering, one render snapshot on one device. Two host models (softbody_group.h):
+// call per tick, state gathered in the caller's numbering, one render snapshot gathered on one device (what happens to it there is
+// render.hpp's state and stage, the same as a single solver's). Two host models (softbody_group.h):
 // a thread per rank (default) or the calling thread walking the tick program step by step across the ranks (SB_GROUP_WALK).
 #include "solver_internal.hpp"
 
@@ -102,40 +103,9 @@ struct sb_group {
     std::vector<std::vector<float>> kin_pos;
     std::vector<int32_t> owner;                  // [n] caller numbering -> owning rank (after finalize)
     std::vector<int32_t> index_in_rank;          // [n] caller numbering -> index in the owner's numbering
-    // ---- render readback, gathered on the render device (rank 0's) ----
-    static constexpr int kSnapSlots = 3;
-    std::vector<int32_t> render_tri, render_set;
-    bool render_dirty = false, render_set_only = false;
-    hipStream_t copy_stream = nullptr;
-    DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri, d_render_set;
-    DevBuf<float> d_gather[kSnapSlots], d_nrm[kSnapSlots], d_cpos[kSnapSlots];
-    float *h_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_nrm[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_cpos[kSnapSlots] = {nullptr, nullptr, nullptr};
-    size_t h_nrm_cap = 0, h_cpos_cap = 0;
-    hipEvent_t ev_copied[kSnapSlots] = {nullptr, nullptr, nullptr};
-    bool snap_compact[kSnapSlots] = {false, false, false}, snap_has_normals[kSnapSlots] = {false, false, false};
-    int snap_head = 0, snap_pending = 0, snap_last_ended = -1;
-    // embedded render vertices (sb_group_set_render_embedding, SPEC.md 6b): cage in the whole mesh's numbering; excludes render_tri
-    int32_t emb_m = 0;
-    std::vector<int32_t> emb_cage, emb_tri;
-    std::vector<float> emb_w;
-    bool emb_dirty = false;
-    DevBuf<int4> d_emb_cage;
-    DevBuf<float4> d_emb_w;
-    DevBuf<int32_t> d_emb_tri, d_emb_adj_off, d_emb_adj_tri;
-    DevBuf<float> d_emb_pos[kSnapSlots], d_emb_nrm[kSnapSlots];
-    float *h_emb_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_emb_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
-    bool snap_embedded[kSnapSlots] = {false, false, false};
-    RenderTangents tan;                          // render tangents of either mode (sb_group_set_render_uvs, SPEC.md 6c), on the render device
-    ReadbackBounds bnd;                          // bounding box of the delivered array (sb_group_set_readback_bounds, SPEC.md 6d), on the render device
-    void release_embedding() {                   // on the render device; no readback is pending when the embedding changes
-        d_emb_cage.free(); d_emb_w.free(); d_emb_tri.free(); d_emb_adj_off.free(); d_emb_adj_tri.free();
-        for (int k = 0; k < kSnapSlots; ++k) {
-            d_emb_pos[k].free(); d_emb_nrm[k].free();
-            if (h_emb_pos[k]) (void)hipHostFree(h_emb_pos[k]);
-            if (h_emb_nrm[k]) (void)hipHostFree(h_emb_nrm[k]);
-            h_emb_pos[k] = h_emb_nrm[k] = nullptr;
-        }
-    }
+    // ---- render readback, gathered on the render device (rank 0's): render.pos[k] is the buffer every rank snapshots into; with an
+    // embedding (SPEC.md 6b) the cage is in the whole mesh's numbering ----
+    RenderState render;
     struct RankRender {                          // per rank, on the rank's device
         DevBuf<int32_t> d_target_of_local;       // owned particle l -> caller id (full snapshots)
         DevBuf<int32_t> d_rs_ids, d_rs_local;    // the render particles (or, with an embedding, the cage particles) the rank owns: caller id, device index
@@ -160,19 +130,10 @@ struct sb_group {
             for (sb_solver *s : ranks) if (s && s->finalized) (void)sb_synchronize(s);
         }
         if (!devices.empty()) (void)hipSetDevice(devices[0]);
-        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-        for (int k = 0; k < kSnapSlots; ++k) {
-            if (h_pos[k]) (void)hipHostFree(h_pos[k]);
-            if (h_nrm[k]) (void)hipHostFree(h_nrm[k]);
-            if (h_cpos[k]) (void)hipHostFree(h_cpos[k]);
-            if (ev_copied[k]) (void)hipEventDestroy(ev_copied[k]);
-            d_gather[k].free(); d_nrm[k].free(); d_cpos[k].free();
-        }
-        d_tri.free(); d_adj_off.free(); d_adj_tri.free(); d_render_set.free();
-        release_embedding();
-        tan.release();
-        bnd.release();
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+        if (render.copy_stream) (void)hipStreamSynchronize(render.copy_stream);
+        for (hipEvent_t e : render.ev_copied) if (e) (void)hipEventDestroy(e);
+        render.release();
+        if (render.copy_stream) (void)hipStreamDestroy(render.copy_stream);
         for (size_t r = 0; r < rr.size(); ++r) {
             (void)hipSetDevice(devices[r]);
             for (int k = 0; k < kSnapSlots; ++k) if (rr[r].ev_snap[k]) (void)hipEventDestroy(rr[r].ev_snap[k]);
@@ -665,80 +626,106 @@ int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const floa
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {
     if (!g || m < 0 || (m > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: bad argument");
     if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_triangles before sb_group_set_particles");
-    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_render_triangles while a readback is pending");
-    if (m > 0 && g->emb_m > 0)
+    if (g->render.pending) return fail(SB_ERR_STATE, "sb_group_set_render_triangles while a readback is pending");
+    if (m > 0 && g->render.emb.m > 0)
         return fail(SB_ERR_STATE, "sb_group_set_render_triangles: a render embedding is set (switch it off first: sb_group_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
-        for (int64_t c = 0; c < 3 * (int64_t)m; ++c) if (tri[c] < 0 || tri[c] >= g->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: particle index out of range");
-        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        g->tan.clear();         // every call that is accepted clears the UVs (sb_group_set_render_uvs)
-        g->render_tri.assign(tri, tri + 3 * (size_t)m);
-        g->render_dirty = true;
-        if (m == 0) g->render_set_only = false;
-        for (bool &b : g->snap_has_normals) b = false;
-        return SB_OK;
+        if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        return set_render_triangles("sb_group_set_render_triangles", g->render, g->n, tri, m);
     });
 }
 
 int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_embedding: null group");
     if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_embedding before sb_group_set_particles");
-    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_render_embedding while a readback is pending");
-    if (m_vertices > 0 && !g->render_tri.empty())
+    if (g->render.pending) return fail(SB_ERR_STATE, "sb_group_set_render_embedding while a readback is pending");
+    if (m_vertices > 0 && !g->render.tri.empty())
         return fail(SB_ERR_STATE, "sb_group_set_render_embedding: render triangles are set (switch them off first: sb_group_set_render_triangles with m = 0)");
     return guarded([&]() -> int {
-        if (int rc = check_embedding_args("sb_group_set_render_embedding", g->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri)) return rc;
-        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        g->tan.clear();         // every call that is accepted clears the UVs (sb_group_set_render_uvs)
-        if (m_vertices == 0 && g->emb_m == 0) return SB_OK;      // off already
-        std::vector<int32_t> cage(cage_ijkl, cage_ijkl + 4 * (size_t)m_vertices), tri(tri_abc, tri_abc + 3 * (size_t)m_tri);
-        std::vector<float> w(weights4, weights4 + 4 * (size_t)m_vertices);
-        if (g->copy_stream) {
-            HIP_CHECK(hipSetDevice(g->device_of(0)));
-            HIP_CHECK(hipStreamSynchronize(g->copy_stream));
-            g->release_embedding();     // (pointers handed out by earlier readbacks of the embedding end here)
-        }
-        g->emb_cage.swap(cage); g->emb_w.swap(w); g->emb_tri.swap(tri);
-        g->emb_m = m_vertices;
-        g->emb_dirty = m_vertices > 0;
-        for (sb_solver *s : g->ranks) if (s) s->n_peek_tiles = -1;
-        for (bool &b : g->snap_has_normals) b = false;
-        if (g->snap_last_ended >= 0 && g->snap_embedded[g->snap_last_ended]) g->snap_last_ended = -1;
-        return SB_OK;
+        if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        const bool was_on = g->render.emb.m > 0;
+        const int rc = set_render_embedding("sb_group_set_render_embedding", g->render, g->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri);
+        if (rc == SB_OK && (was_on || m_vertices > 0)) for (sb_solver *s : g->ranks) if (s) s->n_peek_tiles = -1;
+        return rc;
     });
 }
 
 int sb_group_set_render_uvs(sb_group *g, const float *uv, int32_t count) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_uvs: null group");
     return guarded([&]() -> int {
-        if (g->copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        const int64_t rows = !g->render_tri.empty() ? (int64_t)g->n : (g->emb_m > 0 && !g->emb_tri.empty() ? (int64_t)g->emb_m : -1);
-        return set_render_uvs("sb_group_set_render_uvs", g->tan, uv, count, rows, g->snap_pending != 0);
+        if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
+        return set_render_uvs("sb_group_set_render_uvs", g->render, g->n, uv, count);
     });
 }
 
 int sb_group_set_readback_render_set_only(sb_group *g, int32_t on) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_readback_render_set_only: null group");
-    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_readback_render_set_only while a readback is pending");
-    if (on && g->render_tri.empty()) return fail(SB_ERR_STATE, "sb_group_set_readback_render_set_only: set the render triangles first");
-    g->render_set_only = on != 0;
+    return set_readback_render_set_only("sb_group_set_readback_render_set_only", g->render, on);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The render particles (or, with an embedding, the distinct cage particles), split by owner: caller id and device index, on each rank's device.
+void upload_rank_subsets(sb_group *g, const std::vector<int32_t> &particles) {
+    std::vector<std::vector<int32_t>> ids((size_t)g->W), loc((size_t)g->W);
+    for (int32_t c : particles) {
+        const int r = g->owner[(size_t)c];
+        ids[(size_t)r].push_back(c);
+        loc[(size_t)r].push_back(local_of_old(g->ranks[(size_t)r])[(size_t)g->index_in_rank[(size_t)c]]);
+    }
+    for (int r = 0; r < g->W; ++r) {
+        HIP_CHECK(hipSetDevice(g->device_of(r)));
+        auto &Q = g->rr[(size_t)r];
+        Q.d_rs_ids.upload(ids[(size_t)r], Q.acct); Q.d_rs_local.upload(loc[(size_t)r], Q.acct);
+        Q.rs_local = loc[(size_t)r];
+        g->ranks[(size_t)r]->n_peek_tiles = -1;        // the peek's tile subset follows these particles
+    }
+    HIP_CHECK(hipSetDevice(g->device_of(0)));
+}
+
+// Every rank: tick-end positions (peek or completed tick) of what it owns -- all of it, or its part of the subset -- straight into the
+// gather buffer of slot k on the render device, whose copy stream then waits for all of them.
+int gather_snapshots(sb_group *g, int k, bool subset) {
+    float *dst = g->render.pos[k].d.p;
+    const int rc = g->for_ranks([&](int r) {
+        return guarded([&]() -> int {
+            sb_solver *s = g->ranks[(size_t)r];
+            int rcd = set_device(s); if (rcd) return rcd;
+            auto &Q = g->rr[(size_t)r];
+            const float *src = render_source(s, subset, Q.rs_local);
+            if (subset) launch_snapshot_subset(s, src, Q.d_rs_ids.p, Q.d_rs_local.p, (int)Q.rs_local.size(), dst);
+            else launch_snapshot_all(s, src, Q.d_target_of_local.p, dst);
+            HIP_CHECK(hipEventRecord(Q.ev_snap[k], s->stream));
+            return SB_OK;
+        });
+    });
+    if (rc) return rc;
+    HIP_CHECK(hipSetDevice(g->device_of(0)));
+    for (int r = 0; r < g->W; ++r) HIP_CHECK(hipStreamWaitEvent(g->render.copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
     return SB_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int sb_group_readback_begin(sb_group *g) {
     if (int rc = check_group(g, true, "sb_group_readback_begin")) return rc;
-    if (g->snap_pending == 2) return fail(SB_ERR_STATE, "sb_group_readback_begin: two snapshots already pending, call sb_group_readback_end");
+    if (g->render.pending == 2) return fail(SB_ERR_STATE, "sb_group_readback_begin: two snapshots already pending, call sb_group_readback_end");
     return guarded([&]() -> int {
+        RenderState &R = g->render;
         const int W = g->W, dev0 = g->device_of(0);
         const size_t n3 = (size_t)g->n * 3;
         HIP_CHECK(hipSetDevice(dev0));
-        if (!g->copy_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking));
+        if (!R.copy_stream) {
+            HIP_CHECK(hipStreamCreateWithFlags(&R.copy_stream, hipStreamNonBlocking));
             g->rr.resize((size_t)W);
-            for (int k = 0; k < sb_group::kSnapSlots; ++k) {
-                g->d_gather[k].alloc(n3, g->dev_bytes);
-                HIP_CHECK(hipMemset(g->d_gather[k].p, 0, n3 * sizeof(float)));
-                HIP_CHECK(hipEventCreateWithFlags(&g->ev_copied[k], hipEventDisableTiming));
+            for (int k = 0; k < kSnapSlots; ++k) {
+                R.pos[k].d.alloc(n3, g->dev_bytes);       // (its pinned twin: with the first full snapshot of the slot)
+                HIP_CHECK(hipMemset(R.pos[k].d.p, 0, n3 * sizeof(float)));
+                HIP_CHECK(hipEventCreateWithFlags(&R.ev_copied[k], hipEventDisableTiming));
             }
             for (int r = 0; r < W; ++r) {      // owned particle -> caller id, on the rank's device
                 sb_solver *s = g->ranks[(size_t)r];
@@ -748,237 +735,100 @@ int sb_group_readback_begin(sb_group *g) {
                 std::vector<int32_t> target((size_t)s->n_owned);
                 for (int64_t l = 0; l < s->n_owned; ++l) { const int32_t o = L.local_to_old[(size_t)l]; target[(size_t)l] = map ? map[o] : o; }
                 g->rr[(size_t)r].d_target_of_local.upload(target, g->rr[(size_t)r].acct);
-                for (int k = 0; k < sb_group::kSnapSlots; ++k) HIP_CHECK(hipEventCreateWithFlags(&g->rr[(size_t)r].ev_snap[k], hipEventDisableTiming));
+                for (int k = 0; k < kSnapSlots; ++k) HIP_CHECK(hipEventCreateWithFlags(&g->rr[(size_t)r].ev_snap[k], hipEventDisableTiming));
             }
             HIP_CHECK(hipSetDevice(dev0));
         }
-        const bool compact = g->render_set_only && !g->render_tri.empty();
-        if (!g->render_tri.empty() && g->render_dirty) {     // incident-triangle lists (triangle ids ascending per particle) + who owns which render particle
-            HIP_CHECK(hipStreamSynchronize(g->copy_stream));
-            const int64_t m = (int64_t)g->render_tri.size() / 3;
-            std::vector<int32_t> off((size_t)g->n + 1, 0), adj((size_t)3 * m);
-            for (int64_t c = 0; c < 3 * m; ++c) ++off[(size_t)g->render_tri[c] + 1];
-            g->render_set.clear();
-            for (int32_t v = 0; v < g->n; ++v) { if (off[(size_t)v + 1]) g->render_set.push_back(v); off[(size_t)v + 1] += off[v]; }
-            std::vector<int32_t> cur(off.begin(), off.end() - 1);
-            for (int64_t t = 0; t < m; ++t)
-                for (int j = 0; j < 3; ++j) adj[(size_t)cur[g->render_tri[3 * t + j]]++] = (int32_t)t;
-            g->d_tri.upload(g->render_tri, g->dev_bytes); g->d_adj_off.upload(off, g->dev_bytes); g->d_adj_tri.upload(adj, g->dev_bytes);
-            g->d_render_set.upload(g->render_set, g->dev_bytes);
-            std::vector<std::vector<int32_t>> ids((size_t)W), loc((size_t)W);
-            for (int32_t c : g->render_set) {
-                const int r = g->owner[(size_t)c];
-                ids[(size_t)r].push_back(c);
-                loc[(size_t)r].push_back(local_of_old(g->ranks[(size_t)r])[(size_t)g->index_in_rank[(size_t)c]]);
-            }
-            for (int r = 0; r < W; ++r) {
-                HIP_CHECK(hipSetDevice(g->device_of(r)));
-                auto &R = g->rr[(size_t)r];
-                R.d_rs_ids.upload(ids[(size_t)r], R.acct); R.d_rs_local.upload(loc[(size_t)r], R.acct);
-                R.rs_local = loc[(size_t)r];
-                g->ranks[(size_t)r]->n_peek_tiles = -1;        // the peek's tile subset follows the render set
-            }
-            HIP_CHECK(hipSetDevice(dev0));
-            g->render_dirty = false;
+        const bool compact = R.set_only && !R.tri.empty();
+        if (!R.tri.empty() && R.dirty) {     // the incident-triangle lists, the render set and who owns which of its particles
+            HIP_CHECK(hipStreamSynchronize(R.copy_stream));
+            const std::vector<int32_t> off = R.topo.upload(R.tri, g->n, g->dev_bytes);
+            R.set.clear();
+            for (int32_t v = 0; v < g->n; ++v) if (off[(size_t)v + 1] > off[v]) R.set.push_back(v);
+            R.d_set.upload(R.set, g->dev_bytes);
+            upload_rank_subsets(g, R.set);
+            R.dirty = false;
         }
-        const int k = (g->snap_head + g->snap_pending) % sb_group::kSnapSlots;
-        if (g->emb_m > 0) {
+        const int k = R.next_slot();
+        R.slot[k] = RenderState::Slot{};
+        R.tan.snap_has[k] = false;
+        if (R.emb.m > 0) {
             // Embedded render vertices: every rank snapshots the cage particles it owns into the gather buffer (whole-mesh numbering),
             // then the render device skins the visual mesh from it, computes the normals of the skinned array and copies both out.
-            const size_t m3 = (size_t)g->emb_m * 3;
-            if (g->emb_dirty) {
-                HIP_CHECK(hipStreamSynchronize(g->copy_stream));
-                g->release_embedding();
-                std::vector<int4> cage((size_t)g->emb_m);
-                std::vector<float4> w((size_t)g->emb_m);
+            RenderEmbedding &E = R.emb;
+            if (E.dirty) {
+                HIP_CHECK(hipStreamSynchronize(R.copy_stream));
+                std::vector<int4> cage((size_t)E.m);
                 std::vector<uint8_t> seen((size_t)g->n, 0);
-                std::vector<std::vector<int32_t>> ids((size_t)W), loc((size_t)W);
-                for (int32_t v = 0; v < g->emb_m; ++v) {
-                    const int32_t *c = &g->emb_cage[4 * (size_t)v];
-                    const float *ww = &g->emb_w[4 * (size_t)v];
+                std::vector<int32_t> distinct;
+                for (int32_t v = 0; v < E.m; ++v) {
+                    const int32_t *c = &E.cage[4 * (size_t)v];
                     cage[(size_t)v] = make_int4(c[0], c[1], c[2], c[3]);
-                    w[(size_t)v] = make_float4(ww[0], ww[1], ww[2], ww[3]);
-                    for (int j = 0; j < 4; ++j) {
-                        if (seen[(size_t)c[j]]) continue;
-                        seen[(size_t)c[j]] = 1;
-                        const int r = g->owner[(size_t)c[j]];
-                        ids[(size_t)r].push_back(c[j]);
-                        loc[(size_t)r].push_back(local_of_old(g->ranks[(size_t)r])[(size_t)g->index_in_rank[(size_t)c[j]]]);
-                    }
+                    for (int j = 0; j < 4; ++j) if (!seen[(size_t)c[j]]) { seen[(size_t)c[j]] = 1; distinct.push_back(c[j]); }
                 }
-                g->d_emb_cage.upload(cage, g->dev_bytes); g->d_emb_w.upload(w, g->dev_bytes);
-                if (!g->emb_tri.empty()) {
-                    std::vector<int32_t> off, adj;
-                    build_adjacency(g->emb_tri, g->emb_m, off, adj);
-                    g->d_emb_tri.upload(g->emb_tri, g->dev_bytes); g->d_emb_adj_off.upload(off, g->dev_bytes); g->d_emb_adj_tri.upload(adj, g->dev_bytes);
-                }
-                for (int q = 0; q < sb_group::kSnapSlots; ++q) {
-                    g->d_emb_pos[q].alloc(m3, g->dev_bytes);
-                    HIP_CHECK(hipHostMalloc((void **)&g->h_emb_pos[q], m3 * sizeof(float), hipHostMallocDefault));
-                    if (!g->emb_tri.empty()) {
-                        g->d_emb_nrm[q].alloc(m3, g->dev_bytes);
-                        HIP_CHECK(hipHostMalloc((void **)&g->h_emb_nrm[q], m3 * sizeof(float), hipHostMallocDefault));
-                    }
-                }
-                for (int r = 0; r < W; ++r) {
-                    HIP_CHECK(hipSetDevice(g->device_of(r)));
-                    auto &R = g->rr[(size_t)r];
-                    R.d_rs_ids.upload(ids[(size_t)r], R.acct); R.d_rs_local.upload(loc[(size_t)r], R.acct);
-                    R.rs_local = loc[(size_t)r];
-                    g->ranks[(size_t)r]->n_peek_tiles = -1;        // the peek's tile subset follows the cage particles
-                }
-                HIP_CHECK(hipSetDevice(dev0));
-                g->emb_dirty = false;
+                E.upload(cage, g->dev_bytes);
+                upload_rank_subsets(g, distinct);
             }
-            float *gather = g->d_gather[k].p;
-            int rce = g->for_ranks([&](int r) {
-                return guarded([&]() -> int {
-                    sb_solver *s = g->ranks[(size_t)r];
-                    int rcd = set_device(s); if (rcd) return rcd;
-                    auto &R = g->rr[(size_t)r];
-                    const float *src = render_source(s, /*compact=*/true, R.rs_local);
-                    launch_snapshot_subset(s, src, R.d_rs_ids.p, R.d_rs_local.p, (int)R.rs_local.size(), gather);
-                    HIP_CHECK(hipEventRecord(R.ev_snap[k], s->stream));
-                    return SB_OK;
-                });
-            });
-            if (rce) return rce;
-            HIP_CHECK(hipSetDevice(dev0));
-            for (int r = 0; r < W; ++r) HIP_CHECK(hipStreamWaitEvent(g->copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
-            launch_skin(g->copy_stream, gather, g->d_emb_cage.p, g->d_emb_w.p, g->d_emb_pos[k].p, (int)g->emb_m);
-            HIP_CHECK(hipMemcpyAsync(g->h_emb_pos[k], g->d_emb_pos[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-            g->snap_has_normals[k] = false; g->tan.snap_has[k] = false;
-            if (!g->emb_tri.empty()) {
-                if (g->tan.on()) {      // SPEC.md 6c: normals and tangents in one walk
-                    g->tan.prepare(g->emb_tri, (size_t)g->emb_m, g->dev_bytes);
-                    launch_normals_tangents(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->tan.d_k.p, g->d_emb_nrm[k].p,
-                                            g->tan.d_tan[k].p, (int)g->emb_m, nullptr, nullptr);
-                    HIP_CHECK(hipMemcpyAsync(g->tan.h_tan[k], g->tan.d_tan[k].p, (size_t)g->emb_m * sizeof(float4), hipMemcpyDeviceToHost, g->copy_stream));
-                    g->tan.snap_has[k] = true;
-                } else
-                    launch_normals(g->copy_stream, g->d_emb_pos[k].p, g->d_emb_adj_off.p, g->d_emb_adj_tri.p, g->d_emb_tri.p, g->d_emb_nrm[k].p, (int)g->emb_m, nullptr, nullptr);
-                HIP_CHECK(hipMemcpyAsync(g->h_emb_nrm[k], g->d_emb_nrm[k].p, m3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-                g->snap_has_normals[k] = true;
+            if (int rc = gather_snapshots(g, k, /*subset=*/true)) return rc;
+            launch_skin(R.copy_stream, R.pos[k].d.p, E.d_cage.p, E.d_w.p, E.pos[k].d.p, (int)E.m);
+            E.pos[k].copy_out(R.copy_stream, (size_t)E.m * 3);
+            R.slot[k].embedded = true;
+            if (!E.tri.empty()) launch_normals_stage(R.copy_stream, R, k, E.pos[k].d.p, (int)E.m, false, (size_t)E.m, g->dev_bytes);
+            launch_bounds_stage(R.copy_stream, R.bnd, k, E.pos[k].d.p, nullptr, E.m, g->dev_bytes);      // SPEC.md 6d on the skinned vertices
+        } else {
+            const int count = compact ? (int)R.set.size() : (int)g->n;
+            // this slot's buffers, by what it will carry (they only grow)
+            if (!compact && !R.pos[k].h) R.pos[k].pin();
+            if (!R.tri.empty()) {
+                if (R.nrm[k].d.count < (size_t)count * 3) R.nrm[k].alloc((size_t)count * 3, g->dev_bytes);
+                if (compact && R.cpos[k].d.count < (size_t)count * 3) R.cpos[k].alloc((size_t)count * 3, g->dev_bytes);
             }
-            g->snap_compact[k] = false; g->snap_embedded[k] = true;
-            g->bnd.snap_has[k] = g->bnd.enabled;
-            if (g->bnd.enabled) launch_bounds(g->copy_stream, g->bnd, k, g->d_emb_pos[k].p, nullptr, g->emb_m, g->dev_bytes);      // SPEC.md 6d on the skinned vertices
-            HIP_CHECK(hipEventRecord(g->ev_copied[k], g->copy_stream));
-            ++g->snap_pending;
-            return SB_OK;
-        }
-        g->snap_embedded[k] = false;
-        // host buffers of this slot, by what it will carry
-        if (!compact && !g->h_pos[k]) HIP_CHECK(hipHostMalloc((void **)&g->h_pos[k], n3 * sizeof(float), hipHostMallocDefault));
-        if (!g->render_tri.empty()) {
-            const size_t cnt3 = (compact ? g->render_set.size() : (size_t)g->n) * 3;
-            if (g->d_nrm[k].count < cnt3) g->d_nrm[k].alloc(cnt3, g->dev_bytes);
-            if (compact && g->d_cpos[k].count < cnt3) g->d_cpos[k].alloc(cnt3, g->dev_bytes);
-            // (the pinned buffers of all slots share one capacity: a larger need -- render set changed, or a switch to full snapshots --
-            // frees them all; no readback is pending at such a change)
-            if (g->h_nrm_cap < cnt3) {
-                for (int q = 0; q < sb_group::kSnapSlots; ++q) { if (g->h_nrm[q]) (void)hipHostFree(g->h_nrm[q]); g->h_nrm[q] = nullptr; }
-                g->h_nrm_cap = cnt3;
+            if (int rc = gather_snapshots(g, k, compact)) return rc;
+            if (!compact) R.pos[k].copy_out(R.copy_stream, n3);
+            R.slot[k].compact = compact;
+            if (!R.tri.empty()) {
+                launch_normals_stage(R.copy_stream, R, k, R.pos[k].d.p, count, compact, (size_t)count, g->dev_bytes);
+                R.slot[k].has_render_set = true;
             }
-            if (!g->h_nrm[k]) HIP_CHECK(hipHostMalloc((void **)&g->h_nrm[k], std::max<size_t>(g->h_nrm_cap, 3) * sizeof(float), hipHostMallocDefault));
-            if (compact) {
-                if (g->h_cpos_cap < cnt3) {
-                    for (int q = 0; q < sb_group::kSnapSlots; ++q) { if (g->h_cpos[q]) (void)hipHostFree(g->h_cpos[q]); g->h_cpos[q] = nullptr; }
-                    g->h_cpos_cap = cnt3;
-                }
-                if (!g->h_cpos[k]) HIP_CHECK(hipHostMalloc((void **)&g->h_cpos[k], std::max<size_t>(g->h_cpos_cap, 3) * sizeof(float), hipHostMallocDefault));
-            }
-            if (g->tan.on()) g->tan.prepare(g->render_tri, cnt3 / 3, g->dev_bytes);      // (a larger need frees the slots' buffers, as for the normals)
+            // SPEC.md 6d on the delivered array: every rank's rows are in the gather buffer by now
+            launch_bounds_stage(R.copy_stream, R.bnd, k, compact ? R.cpos[k].d.p : R.pos[k].d.p, nullptr, count, g->dev_bytes);
         }
-        // every rank: tick-end positions (peek or completed tick) of what it owns, straight into the gather buffer on the render device
-        float *dst = g->d_gather[k].p;
-        int rc = g->for_ranks([&](int r) {
-            return guarded([&]() -> int {
-                sb_solver *s = g->ranks[(size_t)r];
-                int rcd = set_device(s); if (rcd) return rcd;
-                auto &R = g->rr[(size_t)r];
-                const float *src = render_source(s, compact, R.rs_local);
-                if (compact) launch_snapshot_subset(s, src, R.d_rs_ids.p, R.d_rs_local.p, (int)R.rs_local.size(), dst);
-                else launch_snapshot_all(s, src, R.d_target_of_local.p, dst);
-                HIP_CHECK(hipEventRecord(R.ev_snap[k], s->stream));
-                return SB_OK;
-            });
-        });
-        if (rc) return rc;
-        HIP_CHECK(hipSetDevice(dev0));
-        for (int r = 0; r < W; ++r) HIP_CHECK(hipStreamWaitEvent(g->copy_stream, g->rr[(size_t)r].ev_snap[k], 0));
-        if (!compact) HIP_CHECK(hipMemcpyAsync(g->h_pos[k], g->d_gather[k].p, n3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-        g->snap_has_normals[k] = false; g->tan.snap_has[k] = false;
-        g->snap_compact[k] = compact;
-        if (!g->render_tri.empty()) {
-            const int count = compact ? (int)g->render_set.size() : (int)g->n;
-            if (g->tan.on()) {      // SPEC.md 6c: normals and tangents in one walk
-                launch_normals_tangents(g->copy_stream, g->d_gather[k].p, g->d_adj_off.p, g->d_adj_tri.p, g->d_tri.p, g->tan.d_k.p, g->d_nrm[k].p, g->tan.d_tan[k].p, count,
-                                        compact ? g->d_render_set.p : (const int32_t *)nullptr, compact ? g->d_cpos[k].p : (float *)nullptr);
-                HIP_CHECK(hipMemcpyAsync(g->tan.h_tan[k], g->tan.d_tan[k].p, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost, g->copy_stream));
-                g->tan.snap_has[k] = true;
-            } else
-                launch_normals(g->copy_stream, g->d_gather[k].p, g->d_adj_off.p, g->d_adj_tri.p, g->d_tri.p, g->d_nrm[k].p, count,
-                               compact ? g->d_render_set.p : (const int32_t *)nullptr, compact ? g->d_cpos[k].p : (float *)nullptr);
-            HIP_CHECK(hipMemcpyAsync(g->h_nrm[k], g->d_nrm[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-            if (compact) HIP_CHECK(hipMemcpyAsync(g->h_cpos[k], g->d_cpos[k].p, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, g->copy_stream));
-            g->snap_has_normals[k] = true;
-        }
-        g->bnd.snap_has[k] = g->bnd.enabled;
-        if (g->bnd.enabled) {       // SPEC.md 6d on the delivered array: every rank's rows are in the gather buffer by now
-            if (compact) launch_bounds(g->copy_stream, g->bnd, k, g->d_cpos[k].p, nullptr, (int64_t)g->render_set.size(), g->dev_bytes);
-            else launch_bounds(g->copy_stream, g->bnd, k, g->d_gather[k].p, nullptr, (int64_t)g->n, g->dev_bytes);
-        }
-        HIP_CHECK(hipEventRecord(g->ev_copied[k], g->copy_stream));
-        ++g->snap_pending;
+        HIP_CHECK(hipEventRecord(R.ev_copied[k], R.copy_stream));
+        ++R.pending;
         return SB_OK;
     });
 }
 
 int sb_group_readback_end(sb_group *g, const float **pos_xyz_out) {
     if (!g || !pos_xyz_out) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_end: null argument");
-    if (g->snap_pending == 0) return fail(SB_ERR_STATE, "sb_group_readback_end without a pending sb_group_readback_begin");
+    if (g->render.pending == 0) return fail(SB_ERR_STATE, "sb_group_readback_end without a pending sb_group_readback_begin");
     return guarded([&]() -> int {
         HIP_CHECK(hipSetDevice(g->device_of(0)));
-        const int k = g->snap_head;
-        HIP_CHECK(hipEventSynchronize(g->ev_copied[k]));
+        HIP_CHECK(hipEventSynchronize(g->render.ev_copied[g->render.head]));
         for (sb_solver *s : g->ranks) check_peer_error(s);
-        *pos_xyz_out = g->snap_embedded[k] ? g->h_emb_pos[k] : (g->snap_compact[k] ? g->h_cpos[k] : g->h_pos[k]);
-        g->snap_last_ended = k;
-        g->snap_head = (g->snap_head + 1) % sb_group::kSnapSlots; --g->snap_pending;
+        *pos_xyz_out = end_slot(g->render);
         return SB_OK;
     });
 }
 
 int sb_group_readback_get_normals(sb_group *g, const float **out) {
     if (!g || !out) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_normals: null argument");
-    if (g->snap_last_ended < 0 || !g->snap_has_normals[g->snap_last_ended])
-        return fail(SB_ERR_STATE, "sb_group_readback_get_normals: no finished readback with render triangles set");
-    *out = g->snap_embedded[g->snap_last_ended] ? g->h_emb_nrm[g->snap_last_ended] : g->h_nrm[g->snap_last_ended];
-    return SB_OK;
+    return readback_get_normals("sb_group_readback_get_normals", g->render, out);
 }
 
 int sb_group_readback_get_tangents(sb_group *g, const float **out) {
     if (!g || !out) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_tangents: null argument");
-    if (g->snap_last_ended < 0 || !g->tan.snap_has[g->snap_last_ended])
-        return fail(SB_ERR_STATE, "sb_group_readback_get_tangents: no finished readback with render UVs set");
-    *out = reinterpret_cast<const float *>(g->tan.h_tan[g->snap_last_ended]);
-    return SB_OK;
+    return readback_get_tangents("sb_group_readback_get_tangents", g->render, out);
 }
 
 int sb_group_set_readback_bounds(sb_group *g, int32_t enabled) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_readback_bounds: null group");
-    if (g->snap_pending) return fail(SB_ERR_STATE, "sb_group_set_readback_bounds while a readback is pending");
-    g->bnd.enabled = enabled != 0;
-    return SB_OK;
+    return set_readback_bounds("sb_group_set_readback_bounds", g->render, enabled);
 }
 
 int sb_group_readback_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
     if (!g || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_bounds: null argument");
-    if (g->snap_last_ended < 0 || !g->bnd.snap_has[g->snap_last_ended])
-        return fail(SB_ERR_STATE, "sb_group_readback_get_bounds: no finished readback that was begun with bounds on (sb_group_set_readback_bounds)");
-    g->bnd.read(g->snap_last_ended, lo_xyz, hi_xyz);
-    return SB_OK;
+    return readback_get_bounds("sb_group_readback_get_bounds", "sb_group_set_readback_bounds", g->render, lo_xyz, hi_xyz);
 }
 
 int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
@@ -1001,12 +851,7 @@ int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
 
 int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids, int32_t *count) {
     if (!g || !ids || !count) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_render_set: null argument");
-    if (g->emb_m > 0) return fail(SB_ERR_STATE, "sb_group_readback_get_render_set: a render embedding is set (the readback brings render vertices, not particles)");
-    if (g->snap_last_ended < 0 || !g->snap_has_normals[g->snap_last_ended])
-        return fail(SB_ERR_STATE, "sb_group_readback_get_render_set: no finished readback with render triangles set");
-    *ids = g->render_set.data();
-    *count = (int32_t)g->render_set.size();
-    return SB_OK;
+    return readback_get_render_set("sb_group_readback_get_render_set", g->render, ids, count);
 }
 
 int sb_group_synchronize(sb_group *g) {

@@ -3,8 +3,9 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
-// tick), readback.hip (state reads / writes, render readback, kinematic targets), validate.hip (table validator), abi.hip (lifecycle,
-// authoring, finalize, stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
+// tick), readback.hip (state reads / writes, kinematic targets), render.hip (render readback: the stage and the entry-point bodies a solver
+// and a group share -- render.hpp -- and the solver's entry points), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
+// stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>      // types and prototypes only: the library itself is bound at run time (RcclApi below)
@@ -108,57 +109,11 @@ struct DevBuf {
     ~DevBuf() { free(); }
 };
 
-// Render tangents (sb_set_render_uvs, SPEC.md 6c) of a solver or of a group's render device: the UVs of the render mode in force, the
-// per-triangle coefficient table made from them, and per snapshot slot the tangents on the device and in pinned memory.
-struct RenderTangents {
-    static constexpr int kSlots = 3;       // (= kSnapSlots of the solver and of the group)
-    std::vector<float> uv;                 // 2 floats per vertex of the render mode in force; empty = tangents off
-    bool dirty = false;                    // UVs changed since the coefficient table was uploaded
-    DevBuf<float4> d_k;                    // (dv2, dv1, du1, du2) / det per triangle, zeros for a UV-degenerate one
-    DevBuf<float4> d_tan[kSlots];
-    float4 *h_tan[kSlots] = {nullptr, nullptr, nullptr};
-    size_t rows = 0;                       // capacity of every slot's buffers
-    bool snap_has[kSlots] = {false, false, false};
-    bool on() const { return !uv.empty(); }
-    void release() {                       // device and pinned buffers (no readback is pending when the UVs or the render mode change)
-        d_k.free();
-        for (int k = 0; k < kSlots; ++k) {
-            d_tan[k].free();
-            if (h_tan[k]) (void)hipHostFree(h_tan[k]);
-            h_tan[k] = nullptr;
-        }
-        rows = 0;
-    }
-    void clear() {                         // tangents off: what every sb_set_render_triangles / sb_set_render_embedding does
-        std::vector<float>().swap(uv);
-        dirty = false;
-        for (bool &b : snap_has) b = false;
-        release();
-    }
-    // before a readback that computes tangents: the coefficient table of `tri` (readback.hip) and buffers of at least n_rows rows
-    void prepare(const std::vector<int32_t> &tri, size_t n_rows, int64_t &acct);
-    ~RenderTangents() { release(); }
-};
+}  // namespace sbi
 
-// Bounding box (sb_set_readback_bounds / sb_get_bounds, SPEC.md 6d) of a solver or of a group's render device: per snapshot slot -- and once
-// more for the synchronous query, which runs on another stream -- the box on the device and in pinned memory, 8 floats: lo.xyz, 0, hi.xyz, 0.
-struct ReadbackBounds {
-    static constexpr int kSlots = 3;       // (= kSnapSlots of the solver and of the group)
-    static constexpr int kQuerySlot = kSlots;
-    bool enabled = false;                  // readbacks begun from now on carry a box
-    DevBuf<float> d_partials;              // the workgroups' boxes: one set for the copy stream, one for the query
-    DevBuf<float> d_box;                   // 8 floats per slot
-    float *h_box = nullptr;
-    bool snap_has[kSlots] = {false, false, false};
-    void prepare(int64_t &acct);           // buffers, at first use (readback.hip)
-    void read(int slot, float lo[3], float hi[3]) const { for (int c = 0; c < 3; ++c) { lo[c] = h_box[8 * slot + c]; hi[c] = h_box[8 * slot + 4 + c]; } }
-    void release() {
-        d_partials.free(); d_box.free();
-        if (h_box) (void)hipHostFree(h_box);
-        h_box = nullptr;
-    }
-    ~ReadbackBounds() { release(); }
-};
+#include "render.hpp"      // the render readback's state (needs DevBuf)
+
+namespace sbi {
 
 struct DevHalo {                 // one halo slot: who we talk to and which particles travel
     std::vector<int> peers;
@@ -314,58 +269,15 @@ struct sb_solver {
         uint32_t *h_error = nullptr;            // pinned host word the kernels set when a wait gives up: the host reads it without a copy
         size_t slot_base(int slot, int world) const { return sbt::mailbox_slot_base(slot, world); }
     } peer;
-    // asynchronous render readback (sb_readback_begin / sb_readback_end): two snapshot slots
-    hipStream_t copy_stream = nullptr;
+    // asynchronous render readback (sb_readback_begin / sb_readback_end; render.hpp): what a group's render device keeps too ...
+    sbi::RenderState render;
+    // ... and what is this rank's own: the snapshot runs on the compute stream, in device numbering
+    hipEvent_t ev_snap[sbi::kSnapSlots] = {nullptr, nullptr, nullptr};
     DevBuf<int32_t> d_local_to_old;
     DevBuf<float> d_get_scratch;           // caller-numbered staging of the blocking sb_get_* calls (world == 1)
-    // three slots, at most two pending: the slot sb_readback_end handed out last is never the next one to be filled, so
-    // its pointer stays valid until the SECOND sb_readback_begin after it (softbody.h)
-    static constexpr int kSnapSlots = 3;
-    DevBuf<float> d_snap[kSnapSlots];
-    float *h_snap[kSnapSlots] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_snap[kSnapSlots] = {nullptr, nullptr, nullptr}, ev_copied[kSnapSlots] = {nullptr, nullptr, nullptr};
-    int snap_head = 0, snap_pending = 0;   // ring: slots snap_head .. snap_head + snap_pending - 1 (mod kSnapSlots) are in flight
-    // render normals of the snapshots (sb_set_render_triangles): incident-triangle lists per particle, caller numbering
-    std::vector<int32_t> render_tri;
-    bool render_dirty = false;             // triangles changed since the last upload
-    DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri, d_render_set, d_render_local;
-    std::vector<int32_t> render_set;       // particles used by the render triangles, ascending
-    bool render_set_only = false;          // readbacks bring the render set only (compact positions + normals)
-    DevBuf<float> d_cpos[kSnapSlots];      // compact positions of the render set
-    float *h_cpos[kSnapSlots] = {nullptr, nullptr, nullptr};
-    bool snap_compact[kSnapSlots] = {false, false, false};
-    DevBuf<float> d_nrm[kSnapSlots];
-    float *h_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
-    bool snap_has_normals[kSnapSlots] = {false, false, false};
-    bool snap_has_render_set[kSnapSlots] = {false, false, false};
-    std::vector<int32_t> render_local;     // device numbering of render_set's particles
-    int snap_last_ended = -1;
-    // embedded render vertices (sb_set_render_embedding, SPEC.md 6b): while emb_m > 0 a readback brings the skinned visual mesh instead of
-    // the particles. Excludes the render triangles above (either mode is switched off before the other is set).
-    struct Embedding {
-        int32_t m = 0;                         // render vertices (0 = off)
-        std::vector<int32_t> cage, tri;        // as given: 4 particles per vertex (caller numbering), triangles over the render vertices
-        std::vector<float> w;                  // 4 weights per vertex
-        bool dirty = false;                    // changed since the last upload
-        std::vector<int32_t> wanted_local;     // the distinct cage particles, device numbering: what a peek has to cover
-        DevBuf<int4> d_cage;                   // device numbering (translated once through local_of_old)
-        DevBuf<float4> d_w;
-        DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri;
-        DevBuf<float> d_pos[kSnapSlots], d_nrm[kSnapSlots];
-        float *h_pos[kSnapSlots] = {nullptr, nullptr, nullptr}, *h_nrm[kSnapSlots] = {nullptr, nullptr, nullptr};
-        void release() {                       // device and pinned buffers (no readback is pending when the embedding changes)
-            d_cage.free(); d_w.free(); d_tri.free(); d_adj_off.free(); d_adj_tri.free();
-            for (int k = 0; k < kSnapSlots; ++k) {
-                d_pos[k].free(); d_nrm[k].free();
-                if (h_pos[k]) (void)hipHostFree(h_pos[k]);
-                if (h_nrm[k]) (void)hipHostFree(h_nrm[k]);
-                h_pos[k] = h_nrm[k] = nullptr;
-            }
-        }
-    } emb;
-    bool snap_embedded[kSnapSlots] = {false, false, false};
-    sbi::RenderTangents tan;               // render tangents of either mode (sb_set_render_uvs): d_tan[q] / h_tan[q] / snap_has[q] per snapshot slot
-    sbi::ReadbackBounds bnd;               // bounding box of the readbacks (sb_set_readback_bounds) and of sb_get_bounds
+    DevBuf<int32_t> d_render_local;
+    std::vector<int32_t> render_local;     // device numbering of render.set's particles
+    std::vector<int32_t> cage_local;       // the distinct cage particles of render.emb, device numbering: what a peek has to cover
     // kinematic targets (sb_set_kinematic_positions): a ring of pinned host tables the scatter kernel reads directly; a table is reused
     // only after the kernel that read it has finished (its event)
     static constexpr int kKinSlots = 4;
@@ -408,7 +320,7 @@ struct sb_solver {
         // communicator, then the streams and events.
         if (stream) (void)hipStreamSynchronize(stream);
         if (comm_stream) (void)hipStreamSynchronize(comm_stream);
-        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+        if (render.copy_stream) (void)hipStreamSynchronize(render.copy_stream);
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.second.exec);
         graphs.clear();
         if (comm) (void)sbi::rccl(false).CommDestroy(comm);
@@ -421,17 +333,12 @@ struct sb_solver {
         if (ev_halo) (void)hipEventDestroy(ev_halo);
         if (comm_stream) (void)hipStreamDestroy(comm_stream);
         gcolours.clear(); halos.clear();
-        for (int k = 0; k < kSnapSlots; ++k) {
-            if (h_snap[k]) (void)hipHostFree(h_snap[k]);
-            if (h_nrm[k]) (void)hipHostFree(h_nrm[k]);
-            if (h_cpos[k]) (void)hipHostFree(h_cpos[k]);
+        for (int k = 0; k < sbi::kSnapSlots; ++k) {
             if (ev_snap[k]) (void)hipEventDestroy(ev_snap[k]);
-            if (ev_copied[k]) (void)hipEventDestroy(ev_copied[k]);
+            if (render.ev_copied[k]) (void)hipEventDestroy(render.ev_copied[k]);
         }
-        emb.release();
-        tan.release();
-        bnd.release();
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+        render.release();
+        if (render.copy_stream) (void)hipStreamDestroy(render.copy_stream);
         for (int k = 0; k < kKinSlots; ++k) {
             if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
             if (h_kin_pos[k]) (void)hipHostFree(h_kin_pos[k]);
@@ -482,27 +389,8 @@ int get_state_owned(sb_solver *s, float *out, bool velocity, const int32_t *id_m
 int set_state_from(sb_solver *s, const float *pos, const float *vel, const int32_t *id_map);
 int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t count);
 const float *render_source(sb_solver *s, bool compact, const std::vector<int32_t> &wanted_local);
-void launch_snapshot_all(sb_solver *s, const float *src_xyz, const int32_t *d_target_of_local, float *dst_xyz);
-void launch_snapshot_subset(sb_solver *s, const float *src_xyz, const int32_t *d_ids, const int32_t *d_local, int count, float *dst_xyz);
-void launch_normals(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, float *nrm_xyz, int count,
-                    const int32_t *subset, float *subset_pos_xyz);
-// the same with tangents (SPEC.md 6c): tri_k = RenderTangents::d_k, tan_xyzw one float4 per lane
-void launch_normals_tangents(hipStream_t st, const float *snap_xyz, const int32_t *adj_off, const int32_t *adj_tri, const int32_t *tri, const float4 *tri_k,
-                             float *nrm_xyz, float4 *tan_xyzw, int count, const int32_t *subset, float *subset_pos_xyz);
-void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const float4 *weights, float *out_xyz, int m);
-// SPEC.md 6d on stream st: the box of rows rows[0 .. count) (rows == nullptr: 0 .. count) of a packed xyz array -> the slot's 8 floats on the
-// device, then 32 bytes to the slot's pinned memory. count == 0 gives the empty box.
-void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz, const int32_t *rows, int64_t count, int64_t &acct);
 // sb_get_bounds: the box of the particles this rank owns, on what sb_get_positions would return now (peeks where that peeks)
 int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]);
-// sb_set_render_uvs / sb_group_set_render_uvs: the rules both share. rows = vertices of the triangle-bearing render mode in force (-1: none)
-int set_render_uvs(const char *who, RenderTangents &T, const float *uv, int32_t count, int64_t rows, bool readback_pending);
-// SPEC.md 6c, static part: (dv2, dv1, du1, du2) / det per triangle in f32, zeros where det == 0 or a quotient is not finite
-void tangent_coefficients(const std::vector<float> &uv, const std::vector<int32_t> &tri, std::vector<float4> &k);
-// sb_set_render_embedding / sb_group_set_render_embedding: the argument rules both share (n = particles the cage may name)
-int check_embedding_args(const char *who, int32_t n, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri);
-// incident-triangle lists per vertex, triangle ids ascending (what normals_kernel walks)
-void build_adjacency(const std::vector<int32_t> &tri, int32_t n_vertices, std::vector<int32_t> &off, std::vector<int32_t> &adj);
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)
