@@ -79,6 +79,9 @@ namespace SoftbodyMI355X
         bool haveBounds;
         Vector4[] tangents;                    // non-null: UVs were handed over (sb_group_set_render_uvs) and every readback brings tangents
         bool snapshotPending;
+        int[] hitTriangles;                    // the triangles the plugin casts rays against, in the numbering of positions / normals
+        readonly float[] rayBuffer = new float[8];
+        readonly SbRayHit[] hitBuffer = new SbRayHit[1];
 
         void Start()
         {
@@ -161,6 +164,7 @@ namespace SoftbodyMI355X
                 positions = (Vector3[])visual.Clone(); normals = new Vector3[visual.Length];      // (what FixedUpdate copies the snapshot into)
                 posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
                 mesh.Clear(); mesh.vertices = positions; mesh.triangles = visualTri; mesh.uv = visualMesh.uv;
+                hitTriangles = visualTri;
                 Vector2[] visualUV = visualMesh.uv;
                 if (visualUV != null && visualUV.Length == visual.Length && visualTri.Length >= 3)
                 {
@@ -173,6 +177,7 @@ namespace SoftbodyMI355X
             {
                 SoftbodyNative.Check(SoftbodyNative.sb_group_set_render_triangles(handle, renderTriangles, renderTriangles.Length / 3), "sb_group_set_render_triangles");
                 normals = new Vector3[positions.Length];
+                hitTriangles = renderTriangles;
                 bool withUV = renderUV != null && renderUV.Length == positions.Length;      // one UV per particle (no seams in this mode)
                 if (withUV)
                 {
@@ -195,6 +200,7 @@ namespace SoftbodyMI355X
                     positions = compactPos; normals = new Vector3[compactPos.Length];
                     posPin = GCHandle.Alloc(positions, GCHandleType.Pinned);
                     mesh.Clear(); mesh.vertices = positions; mesh.triangles = tri;
+                    hitTriangles = tri;                       // (same triangles in the same order, over the compact arrays)
                     if (withUV) { mesh.uv = compactUV; tangents = new Vector4[compactPos.Length]; }
                 }
             }
@@ -265,6 +271,31 @@ namespace SoftbodyMI355X
             if (handle != IntPtr.Zero) { SoftbodyNative.sb_group_destroy(handle); handle = IntPtr.Zero; }
         }
 
+        /// <summary>Physics.Raycast for the deforming body, without a MeshCollider to re-bake: the ray (world space) is cast on the GPU against the
+        /// triangles of the snapshot on screen -- the one the last FixedUpdate copied into the mesh -- whatever has been simulated since
+        /// (SPEC.md 6e, sb_group_readback_raycast: synchronous, brute force over every triangle, both faces). Needs asyncReadback and a render mode
+        /// with triangles (renderTriangles or visualMesh); false before the first snapshot has been shown, or where nothing is hit within
+        /// maxDistance. The point and the interpolated normal come from (triangle, u, v) and the arrays the component already holds.</summary>
+        public bool Raycast(Ray ray, float maxDistance, out SoftbodyHit hit)
+        {
+            hit = default(SoftbodyHit);
+            if (handle == IntPtr.Zero || hitTriangles == null || !haveBounds) return false;      // (haveBounds: a snapshot has ended)
+            Vector3 o = transform.InverseTransformPoint(ray.origin), d = transform.InverseTransformVector(ray.direction);      // t stays a world distance
+            rayBuffer[0] = o.x; rayBuffer[1] = o.y; rayBuffer[2] = o.z; rayBuffer[3] = maxDistance;
+            rayBuffer[4] = d.x; rayBuffer[5] = d.y; rayBuffer[6] = d.z; rayBuffer[7] = 0f;
+            SoftbodyNative.Check(SoftbodyNative.sb_group_readback_raycast(handle, rayBuffer, 1, hitBuffer), "sb_group_readback_raycast");
+            SbRayHit h = hitBuffer[0];
+            if (h.triangle < 0) return false;
+            int a = hitTriangles[3 * h.triangle], b = hitTriangles[3 * h.triangle + 1], c = hitTriangles[3 * h.triangle + 2];
+            float wa = 1f - h.u - h.v;
+            hit.triangle = h.triangle; hit.distance = h.t; hit.barycentric = new Vector3(wa, h.u, h.v);
+            hit.point = transform.TransformPoint(wa * positions[a] + h.u * positions[b] + h.v * positions[c]);
+            Vector3 nrm = normals != null ? wa * normals[a] + h.u * normals[b] + h.v * normals[c]
+                                          : Vector3.Cross(positions[b] - positions[a], positions[c] - positions[a]);
+            hit.normal = transform.TransformDirection(nrm).normalized;
+            return true;
+        }
+
         /// <summary>Attachments: move pinned particles (inverse mass 0) to new positions before the next FixedUpdate; their constrained
         /// neighbours are pulled along (SPEC.md 2, sb_group_set_kinematic_positions: every GPU takes the pins it owns). ids index the particle arrays.</summary>
         public void MoveKinematic(int[] ids, Vector3[] targets)
@@ -331,5 +362,14 @@ namespace SoftbodyMI355X
             var h = GCHandle.Alloc(a, GCHandleType.Pinned);
             try { f(h.AddrOfPinnedObject()); } finally { h.Free(); }
         }
+    }
+
+    /// <summary>What Softbody.Raycast found: world-space point and interpolated vertex normal, the distance along the ray, the render triangle
+    /// and the barycentric weights of its three corners.</summary>
+    public struct SoftbodyHit
+    {
+        public Vector3 point, normal, barycentric;
+        public float distance;
+        public int triangle;
     }
 }

@@ -113,6 +113,15 @@ namespace SoftbodyMI355X
         public double packMs, transportMs, totalMs, exposedWaitMs;
     }
 
+    /// <summary>sb_ray_hit (16 bytes): the nearest hit of one ray; triangle = -1 where nothing is hit. t in units of the direction's length,
+    /// (u, v) barycentric: point = (1 - u - v) p[a] + u p[b] + v p[c].</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbRayHit
+    {
+        public int triangle;
+        public float t, u, v;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -167,6 +176,8 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_bounds(IntPtr s, int enabled);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_bounds(IntPtr s, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_get_bounds(IntPtr s, [Out] float[] loXyz, [Out] float[] hiXyz);
+        // rays: 8 floats each = origin xyz, t_max, direction xyz, 0 (SPEC.md 6e)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_raycast(IntPtr s, float[] rays, int count, [Out] SbRayHit[] hits);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_readback_render_set_only(IntPtr s, int renderSetOnly);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_get_render_set(IntPtr s, out IntPtr ids, out int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_get_owner(IntPtr s, IntPtr ownerRankOut, int n);
@@ -230,6 +241,7 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_readback_bounds(IntPtr g, int enabled);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_raycast(IntPtr g, float[] rays, int count, [Out] SbRayHit[] hits);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_rank_count(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_rank(IntPtr g, int rank, out IntPtr solver);

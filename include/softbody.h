@@ -21,7 +21,7 @@
  *    SB_ERR_NO_DEVICE.
  *  - Semantics of one tick: SPEC.md.
  *
- * This header is the whole PRODUCT surface of a solver handle (38 functions). Beside it:
+ * This header is the whole PRODUCT surface of a solver handle (39 functions). Beside it:
  *   softbody_group.h  one process -- a Unity player -- driving several GPUs behind the same component (sb_group_*)
  *   softbody_plan.h   host-only planner inspection (published order, tiles, halo lists; frame / window of sharded authoring)
  *   softbody_debug.h  test hooks, the table validator, per-launch timing and the tuning switches of A/B measurements
@@ -272,6 +272,27 @@ int sb_readback_get_tangents(sb_solver *s, const float **tangent_xyzw_out);
 int sb_set_readback_bounds(sb_solver *s, int32_t enabled);
 int sb_readback_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]);
 int sb_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]);
+/* Ray casts (SPEC.md 6e; replaces re-baking a MeshCollider on the main thread whenever the vertices move, or walking the triangles over the
+ * pinned snapshot): count rays, 8 floats each = origin xyz, t_max, direction xyz, 0, against the deformed render mesh -- the triangles and the
+ * vertex array of the render mode the snapshot was taken in: the render triangles over the snapshot (full or render-set readback: the same
+ * hits), or the embedding's triangles over the skinned vertices. The direction need not be unit length, t is in units of its length, both faces
+ * are hit. hits_out[r] = the nearest hit of ray r with 0 <= t <= t_max (among equal t the smallest triangle index), (u, v) its barycentric
+ * coordinates: point = (1 - u - v) p[a] + u p[b] + v p[c]; triangle = -1 and t = u = v = 0 where nothing is hit. Brute force over every
+ * triangle in two small kernels, no atomics; the bits are those of SPEC.md 6e's sequential loop.
+ *  - Synchronous. It casts against the snapshot the LAST sb_readback_end returned -- the mesh on screen. Later snapshots may be pending and
+ *    later ticks issued: neither changes the answer, and the call neither waits for them nor disturbs them. It runs on a stream of its own
+ *    (not the compute stream, not the copy stream: a pending snapshot's copy does not sit in front of it), leaves the tick's held-back last
+ *    kernel held back and does not peek: sb_stats.readback_peeks and ticks_fused are what they are without it.
+ *  - SB_ERR_STATE: no readback has ended; that snapshot was taken with no triangles in force (full mode without render triangles, an embedding
+ *    with m_tri = 0); or sb_set_render_triangles / sb_set_render_embedding were called since (they invalidate the snapshot's arrays).
+ *  - SB_ERR_INVALID_ARG, nothing written to hits_out: a null handle, count < 0, a null rays or hits_out with count > 0, a NaN or infinite
+ *    origin or direction component, a t_max that is NaN or negative (+inf is allowed). count = 0 returns SB_OK once the state checks pass.
+ *  - A rank of a partitioned solver (world > 1) returns SB_ERR_UNSUPPORTED, for the reason sb_readback_get_normals does
+ *    (sb_group_readback_raycast serves that case).
+ *  - Device and pinned buffers (4 MB, of a fixed batch of 256 rays; larger counts are walked in batches) are allocated at the first cast:
+ *    until then sb_stats.device_bytes is unchanged. */
+typedef struct { int32_t triangle; float t, u, v; } sb_ray_hit;      /* 16 bytes; triangle = -1: no hit */
+int sb_readback_raycast(sb_solver *s, const float *rays /* 8 floats per ray */, int32_t count, sb_ray_hit *hits_out);
 int sb_get_owner(sb_solver *s, int32_t *owner_rank_out, int32_t n);
 
 

@@ -116,6 +116,9 @@ int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids_out, int32
 int sb_group_set_readback_bounds(sb_group *g, int32_t enabled);
 int sb_group_readback_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
 int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
+/* Ray casts (sb_readback_raycast, SPEC.md 6e), same contract, against the snapshot the last sb_group_readback_end returned: on the render
+ * device, on the gathered snapshot (whole array or render set) or the skinned vertices, in both host models -- the ranks take no part. */
+int sb_group_readback_raycast(sb_group *g, const float *rays /* 8 floats per ray */, int32_t count, sb_ray_hit *hits_out);
 
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);

@@ -214,4 +214,104 @@ __global__ __launch_bounds__(kBoundsLanes) void bounds_final_kernel(const float 
     }
 }
 
+// SPEC.md §6e: ray casts against a snapshot's triangles, in two launches and without atomics. A candidate's distance is a non-negative float
+// after its + 0.0f, so its bits order as an unsigned integer and the 64-bit key (bits(t) << 32) | triangle, a miss all ones, is a total
+// order: its minimum is exact, the triangle ids are distinct, so any tree delivers the sequential loop's hit, (u, v) travelling with the key.
+constexpr int kRayLanes = 256;
+constexpr int kRayMaxGroups = 1024;     // grid cap of raycast_partial_kernel along the triangles; larger lists walk the grid-stride loop
+constexpr int kRayTile = 4;             // rays a workgroup tests every triangle against: 4 x (key, u, v) = 16 registers beside the corners
+constexpr int kRayBatch = 256;          // rays per pair of launches: the partials are kRayMaxGroups x kRayBatch x 16 bytes, whatever the count
+constexpr unsigned long long kRayMiss = ~0ull;
+
+struct RayBest { unsigned long long key; float u, v; };
+
+__device__ __forceinline__ void ray_take(RayBest &b, unsigned long long key, float u, float v) {
+    if (key < b.key) { b.key = key; b.u = u; b.v = v; }
+}
+__device__ __forceinline__ uint4 ray_pack(const RayBest &b) {
+    return make_uint4((unsigned)b.key, (unsigned)(b.key >> 32), __float_as_uint(b.u), __float_as_uint(b.v));
+}
+__device__ __forceinline__ RayBest ray_unpack(uint4 q) {
+    return {((unsigned long long)q.y << 32) | q.x, __uint_as_float(q.z), __uint_as_float(q.w)};
+}
+// the wave's minimum in every lane of it
+__device__ __forceinline__ void ray_reduce_wave(RayBest &b) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)b.key, m, 64), hi = __shfl_xor((unsigned)(b.key >> 32), m, 64);
+        const float u = __shfl_xor(b.u, m, 64), v = __shfl_xor(b.v, m, 64);
+        ray_take(b, ((unsigned long long)hi << 32) | lo, u, v);
+    }
+}
+
+// Grid (triangle chunks, ray tiles). Lane k of a chunk row walks triangles k, k + stride, ...: three indices and three 12-byte rows per
+// triangle, gathered once and tested against the kRayTile rays of blockIdx.y. A ray's address is the same in every lane (kernel argument
+// and blockIdx only), so its eight floats arrive by scalar loads and stay in SGPRs. Per ray one key and (u, v) in registers; at the end a
+// wave64 butterfly, the four waves through LDS, and lanes 0 .. kRayTile-1 store the workgroup's partial of one ray each, 16 bytes:
+// partials[ray * gridDim.x + chunk]. The statements are SPEC.md §6e's, in its order (the unit is built with contraction off).
+// n_rays >= 1; gridDim.y = ceil(n_rays / kRayTile); gridDim.x = min(ceil(m / 256), kRayMaxGroups) >= 1.
+__global__ __launch_bounds__(kRayLanes) void raycast_partial_kernel(const float *xyz, const int32_t *tri, int m, const float *rays, int n_rays, uint4 *partials) {
+    __shared__ uint4 wave_best[kRayLanes / 64][kRayTile];
+    const int ray0 = (int)blockIdx.y * kRayTile;
+    RayBest best[kRayTile];
+#pragma unroll
+    for (int j = 0; j < kRayTile; ++j) best[j] = {kRayMiss, 0.0f, 0.0f};
+    const int stride = (int)gridDim.x * kRayLanes;
+    for (int64_t t_id = (int64_t)blockIdx.x * kRayLanes + threadIdx.x; t_id < m; t_id += stride) {
+        const size_t a = 3 * (size_t)tri[3 * t_id], b = 3 * (size_t)tri[3 * t_id + 1], c = 3 * (size_t)tri[3 * t_id + 2];
+        const V3 pa = {xyz[a], xyz[a + 1], xyz[a + 2]};
+        const V3 e1 = sub3({xyz[b], xyz[b + 1], xyz[b + 2]}, pa);
+        const V3 e2 = sub3({xyz[c], xyz[c + 1], xyz[c + 2]}, pa);
+#pragma unroll
+        for (int j = 0; j < kRayTile; ++j) {
+            if (ray0 + j >= n_rays) break;       // (the same in every lane)
+            const float *r = rays + 8 * (size_t)(ray0 + j);
+            const V3 o = {r[0], r[1], r[2]}, d = {r[4], r[5], r[6]};
+            const float tmax = r[3];
+            const V3 P = cross3(d, e2);
+            const float det = dot3(e1, P);
+            if (!(det != 0.0f)) continue;
+            const float inv = 1.0f / det;
+            const V3 T = sub3(o, pa);
+            const float u = dot3(T, P) * inv;
+            if (!(u >= 0.0f && u <= 1.0f)) continue;
+            const V3 Q = cross3(T, e1);
+            const float v = dot3(d, Q) * inv;
+            if (!(v >= 0.0f && (u + v) <= 1.0f)) continue;
+            float t = dot3(e2, Q) * inv;
+            if (!(t >= 0.0f && t <= tmax)) continue;
+            t = t + 0.0f;
+            ray_take(best[j], ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)t_id, u, v);
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < kRayTile; ++j) {
+        ray_reduce_wave(best[j]);
+        if ((threadIdx.x & 63) == 0) wave_best[wave][j] = ray_pack(best[j]);
+    }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j < kRayTile && ray0 + j < n_rays) {
+        RayBest b = ray_unpack(wave_best[0][j]);
+        for (int w = 1; w < kRayLanes / 64; ++w) { const RayBest o = ray_unpack(wave_best[w][j]); ray_take(b, o.key, o.u, o.v); }
+        partials[(size_t)(ray0 + j) * gridDim.x + blockIdx.x] = ray_pack(b);
+    }
+}
+
+// Workgroup r reduces ray r's n_partials partials by key and writes its sb_ray_hit -- triangle, t, u, v; a miss: -1, 0, 0, 0 -- in one
+// 16-byte store.
+__global__ __launch_bounds__(kRayLanes) void raycast_final_kernel(const uint4 *partials, int n_partials, uint4 *hits) {
+    __shared__ uint4 wave_best[kRayLanes / 64];
+    RayBest b = {kRayMiss, 0.0f, 0.0f};
+    const uint4 *mine = partials + (size_t)blockIdx.x * n_partials;
+    for (int g = threadIdx.x; g < n_partials; g += kRayLanes) { const RayBest o = ray_unpack(mine[g]); ray_take(b, o.key, o.u, o.v); }
+    ray_reduce_wave(b);
+    if ((threadIdx.x & 63) == 0) wave_best[threadIdx.x >> 6] = ray_pack(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kRayLanes / 64; ++w) { const RayBest o = ray_unpack(wave_best[w]); ray_take(b, o.key, o.u, o.v); }
+        hits[blockIdx.x] = b.key == kRayMiss ? make_uint4(0xffffffffu, 0u, 0u, 0u) : make_uint4((unsigned)b.key, (unsigned)(b.key >> 32), __float_as_uint(b.u), __float_as_uint(b.v));
+    }
+}
+
 }  // namespace sbk

@@ -62,6 +62,16 @@ void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz
     HIP_CHECK(hipMemcpyAsync(B.box.h + 8 * (size_t)slot, B.box.d.p + 8 * (size_t)slot, 8 * sizeof(float), hipMemcpyDeviceToHost, st));
 }
 
+static_assert(sizeof(sb_ray_hit) == sizeof(uint4), "raycast_final_kernel writes an sb_ray_hit as one 16-byte store");
+
+void ReadbackRaycast::prepare(int64_t &acct) {
+    if (stream) return;
+    rays.alloc((size_t)8 * sbk::kRayBatch, acct);
+    hits.alloc((size_t)sbk::kRayBatch, acct);
+    d_partials.alloc((size_t)sbk::kRayMaxGroups * sbk::kRayBatch, acct);
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+}
+
 // SPEC.md 6c, static part: (dv2, dv1, du1, du2) / det per triangle in f32, zeros where det == 0 or a quotient is not finite. Host code of a
 // unit built with contraction off: two rounded products and one subtraction for det, four IEEE divisions.
 static void tangent_coefficients(const std::vector<float> &uv, const std::vector<int32_t> &tri, std::vector<float4> &k) {
@@ -247,6 +257,44 @@ int readback_get_render_set(const char *who, RenderState &R, const int32_t **ids
     if (R.last_ended < 0 || !R.slot[R.last_ended].has_render_set) return fail(SB_ERR_STATE, std::string(who) + ": no finished readback with render triangles set");
     *ids = R.set.data();
     *count = (int32_t)R.set.size();
+    return SB_OK;
+}
+
+int readback_raycast(const char *who, RenderState &R, const float *rays, int32_t count, sb_ray_hit *hits_out, int64_t &acct) {
+    const std::string me(who);
+    if (count < 0) return fail(SB_ERR_INVALID_ARG, me + ": negative count");
+    if (count > 0 && (!rays || !hits_out)) return fail(SB_ERR_INVALID_ARG, me + ": null pointer with a positive count");
+    for (int64_t r = 0; r < count; ++r) {       // every ray before anything is written
+        const float *q = rays + 8 * r;
+        for (int c : {0, 1, 2, 4, 5, 6})
+            if (!std::isfinite(q[c])) return fail(SB_ERR_INVALID_ARG, me + ": origin or direction is NaN or infinite (ray " + std::to_string(r) + ")");
+        if (!(q[3] >= 0.0f)) return fail(SB_ERR_INVALID_ARG, me + ": t_max is NaN or negative (ray " + std::to_string(r) + ")");
+    }
+    // the snapshot ended last, where it was taken with triangles in force and they were not set again since (has_normals says both)
+    const int k = R.last_ended;
+    if (k < 0) return fail(SB_ERR_STATE, me + ": no readback has ended");
+    if (!R.slot[k].has_normals)
+        return fail(SB_ERR_STATE, me + ": the snapshot ended last has no triangles to cast against (taken without render triangles, or the render mode was set again since)");
+    if (count == 0) return SB_OK;
+    const bool embedded = R.slot[k].embedded;
+    const float *xyz = embedded ? R.emb.pos[k].d.p : R.pos[k].d.p;        // (a compact snapshot wrote the render set's rows of the caller-numbered array)
+    const RenderTopology &T = embedded ? R.emb.topo : R.topo;
+    const int m = (int)((embedded ? R.emb.tri.size() : R.tri.size()) / 3);
+    ReadbackRaycast &Q = R.ray;
+    Q.prepare(acct);
+    const int groups = (int)std::min<int64_t>(((int64_t)m + sbk::kRayLanes - 1) / sbk::kRayLanes, sbk::kRayMaxGroups);
+    for (int64_t done = 0; done < count; done += sbk::kRayBatch) {
+        const int nb = (int)std::min<int64_t>(count - done, sbk::kRayBatch);
+        std::memcpy(Q.rays.h, rays + 8 * done, (size_t)nb * 8 * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(Q.rays.d.p, Q.rays.h, (size_t)nb * 8 * sizeof(float), hipMemcpyHostToDevice, Q.stream));
+        hipLaunchKernelGGL(sbk::raycast_partial_kernel, dim3((unsigned)groups, (unsigned)((nb + sbk::kRayTile - 1) / sbk::kRayTile)), dim3(sbk::kRayLanes), 0, Q.stream, xyz,
+                           T.d_tri.p, m, Q.rays.d.p, nb, Q.d_partials.p);
+        hipLaunchKernelGGL(sbk::raycast_final_kernel, dim3((unsigned)nb), dim3(sbk::kRayLanes), 0, Q.stream, Q.d_partials.p, groups, Q.hits.d.p);
+        HIP_CHECK(hipGetLastError());
+        Q.hits.copy_out(Q.stream, (size_t)nb);
+        HIP_CHECK(hipStreamSynchronize(Q.stream));
+        std::memcpy(hits_out + done, Q.hits.h, (size_t)nb * sizeof(sb_ray_hit));
+    }
     return SB_OK;
 }
 
@@ -446,6 +494,17 @@ int sb_set_readback_bounds(sb_solver *s, int32_t enabled) {
 int sb_readback_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]) {
     if (!s || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_readback_get_bounds: null argument");
     return readback_get_bounds("sb_readback_get_bounds", "sb_set_readback_bounds", s->render, lo_xyz, hi_xyz);
+}
+
+int sb_readback_raycast(sb_solver *s, const float *rays, int32_t count, sb_ray_hit *hits_out) {
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_readback_raycast: null handle");
+    if (s->desc.world > 1)
+        return fail(SB_ERR_UNSUPPORTED, "sb_readback_raycast: a rank of a partitioned solver does not hold its neighbours' particles; rays against a partitioned "
+                    "body are cast on the gathered snapshot (sb_group_readback_raycast)");
+    return guarded([&]() -> int {
+        if (s->finalized) { int rc = set_device(s); if (rc) return rc; }
+        return readback_raycast("sb_readback_raycast", s->render, rays, count, hits_out, s->dev_bytes);
+    });
 }
 
 int sb_set_readback_render_set_only(sb_solver *s, int32_t on) {

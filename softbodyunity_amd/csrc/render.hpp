@@ -71,6 +71,21 @@ struct ReadbackBounds {
     void release() { d_partials.free(); box.release(); }
 };
 
+// Ray casts (sb_readback_raycast, SPEC.md 6e): a stream of its own -- a cast waits for no pending snapshot's copy -- and, from the first cast
+// on, the buffers of one batch of rays: the rays and the hits with their pinned twins, the workgroups' partials. Larger counts walk in batches.
+struct ReadbackRaycast {
+    hipStream_t stream = nullptr;
+    Mirror<float> rays;                    // 8 floats per ray of a batch (the pinned side is the staging of the upload)
+    Mirror<uint4> hits;                    // one sb_ray_hit per ray of a batch
+    DevBuf<uint4> d_partials;              // (key, u, v) per (ray, workgroup)
+    void prepare(int64_t &acct);           // stream and buffers, at first use
+    void release() {
+        rays.release(); hits.release(); d_partials.free();
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
+
 // Triangles and the incident-triangle lists per vertex (triangle ids ascending: what the normals kernels walk), on the device.
 struct RenderTopology {
     DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri;
@@ -119,11 +134,12 @@ struct RenderState {
     RenderEmbedding emb;
     RenderTangents tan;                    // of either mode
     ReadbackBounds bnd;                    // of the delivered array, and of the synchronous query
+    ReadbackRaycast ray;                   // casts against the snapshot ended last
     void forget_normals() { for (Slot &q : slot) q.has_normals = q.has_render_set = false; }
     void release() {                       // every buffer, with the copy stream idle (the owner's destructor)
         topo.release(); d_set.free();
         for (int k = 0; k < kSnapSlots; ++k) { pos[k].release(); nrm[k].release(); cpos[k].release(); }
-        emb.release(); tan.release(); bnd.release();
+        emb.release(); tan.release(); bnd.release(); ray.release();
     }
 };
 
@@ -156,5 +172,7 @@ int readback_get_normals(const char *who, RenderState &R, const float **out);
 int readback_get_tangents(const char *who, RenderState &R, const float **out);
 int readback_get_bounds(const char *who, const char *setter, RenderState &R, float lo_xyz[3], float hi_xyz[3]);      // setter: the name the message points to
 int readback_get_render_set(const char *who, RenderState &R, const int32_t **ids, int32_t *count);
+// SPEC.md 6e behind the owner's null-handle, world and device preconditions: `count` rays against the snapshot ended last, synchronous
+int readback_raycast(const char *who, RenderState &R, const float *rays, int32_t count, sb_ray_hit *hits_out, int64_t &acct);
 
 }  // namespace sbi

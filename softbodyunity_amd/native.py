@@ -99,6 +99,11 @@ class SbPhaseInfo(C.Structure):
                 ("order_begin", C.c_int64), ("order_end", C.c_int64), ("task_begin", C.c_int64), ("task_end", C.c_int64)]
 
 
+class SbRayHit(C.Structure):
+    """sb_ray_hit (16 bytes): triangle = -1 where nothing is hit"""
+    _fields_ = [("triangle", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -134,6 +139,7 @@ SIGNATURES = {
     "sb_set_readback_bounds": (C.c_int, [_P, C.c_int32]),
     "sb_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sb_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
     "sb_set_readback_render_set_only": (C.c_int, [_P, C.c_int32]),
     "sb_readback_get_render_set": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
     "sb_get_owner": (C.c_int, [_P, _P, C.c_int32]),
@@ -199,6 +205,7 @@ SIGNATURES = {
     "sb_group_set_readback_bounds": (C.c_int, [_P, C.c_int32]),
     "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sb_group_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
     "sb_group_synchronize": (C.c_int, [_P]),
     "sb_group_rank_count": (C.c_int32, [_P]),
     "sb_group_get_rank": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

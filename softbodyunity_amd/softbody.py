@@ -213,6 +213,12 @@ class Softbody:
         """-> (lo, hi), float32 (3,): the box of the particles this rank owns, on what get_positions() would return now (SPEC.md 6d)."""
         return _box(native.lib().sb_get_bounds, self._h)
 
+    def raycast(self, rays):
+        """Rays against the deformed render mesh of the snapshot readback_end returned last (SPEC.md 6e). rays: (R, 8) float32 = origin xyz,
+        t_max, direction xyz, 0 -- or (R, 7) without the last column. -> structured array (R,) with fields triangle (int32, -1 = no hit),
+        t, u, v (float32): the nearest hit, t in units of the direction's length, (u, v) barycentric in the triangle's corners b and c."""
+        return _raycast(native.lib().sb_readback_raycast, self._h, rays)
+
     def set_readback_render_set_only(self, on=True):
         """Readbacks bring only the particles the render triangles use (compact arrays)."""
         check(native.lib().sb_set_readback_render_set_only(self._h, 1 if on else 0))
@@ -323,6 +329,21 @@ def _box(fn, handle):
     lo = np.zeros(3, np.float32); hi = np.zeros(3, np.float32)
     check(fn(handle, _fp(lo), _fp(hi)))
     return lo, hi
+
+
+RAY_HIT = np.dtype([("triangle", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
+
+
+def _raycast(fn, handle, rays):
+    """hits of one of the *_readback_raycast entry points"""
+    rays = np.asarray(rays, dtype=np.float32)
+    assert rays.ndim == 2 and rays.shape[1] in (7, 8), "rays: (R, 8) = origin xyz, t_max, direction xyz, 0 -- or (R, 7)"
+    if rays.shape[1] == 7:
+        rays = np.concatenate([rays, np.zeros((rays.shape[0], 1), np.float32)], axis=1)
+    rays = np.ascontiguousarray(rays)
+    hits = np.zeros(rays.shape[0], RAY_HIT)
+    check(fn(handle, _fp(rays), rays.shape[0], hits.ctypes.data_as(C.POINTER(native.SbRayHit))))
+    return hits
 
 
 def _uv_args(uv):
@@ -505,6 +526,10 @@ class SoftbodyGroup:
     def set_readback_bounds(self, on=True):
         """Softbody.set_readback_bounds on the array the group delivers."""
         check(native.lib().sb_group_set_readback_bounds(self._g, 1 if on else 0))
+
+    def raycast(self, rays):
+        """Softbody.raycast against the snapshot the group delivered last, on the render device."""
+        return _raycast(native.lib().sb_group_readback_raycast, self._g, rays)
 
     def get_bounds(self):
         """-> (lo, hi): every rank's box of what it owns, combined on the host."""
