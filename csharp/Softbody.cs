@@ -82,6 +82,8 @@ namespace SoftbodyMI355X
         int[] hitTriangles;                    // the triangles the plugin casts rays against, in the numbering of positions / normals
         readonly float[] rayBuffer = new float[8];
         readonly SbRayHit[] hitBuffer = new SbRayHit[1];
+        SbImpulse[] impulseQueue = new SbImpulse[16];      // AddImpulse / AddImpulseAtHit / AddExplosionImpulse since the last FixedUpdate, in call order
+        int impulseCount;
 
         void Start()
         {
@@ -208,6 +210,7 @@ namespace SoftbodyMI355X
 
         void FixedUpdate()
         {
+            SendImpulses();      // everything queued since the last tick, in one call, before the step
             if (useGpu && asyncReadback)
             {
                 // show the snapshot taken after the PREVIOUS tick (its copy and its normals ran beside this tick's kernels),
@@ -294,6 +297,51 @@ namespace SoftbodyMI355X
                                           : Vector3.Cross(positions[b] - positions[a], positions[c] - positions[a]);
             hit.normal = transform.TransformDirection(nrm).normalized;
             return true;
+        }
+
+        /// <summary>Rigidbody.AddForce(impulse, ForceMode.Impulse) for one particle (velocityChange: ForceMode.VelocityChange -- the mass is
+        /// ignored). World-space vector; queued, sent with the next FixedUpdate before the step (SPEC.md 2c). A pinned particle takes nothing.</summary>
+        public void AddImpulse(int particle, Vector3 impulse, bool velocityChange = false)
+        {
+            if (particle < 0 || particle >= inverseMass.Length) throw new ArgumentOutOfRangeException(nameof(particle));
+            Vector3 j = transform.InverseTransformVector(impulse);
+            Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_PARTICLE, flags = velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u,
+                                  index = particle, vecX = j.x, vecY = j.y, vecZ = j.z });
+        }
+
+        /// <summary>Rigidbody.AddForceAtPosition for what Raycast found: the impulse is shared among the hit triangle's corners by the hit's
+        /// barycentric weights (with a visual mesh: on to the cage particles behind each corner, by the skinning weights).</summary>
+        public void AddImpulseAtHit(SoftbodyHit hit, Vector3 impulse, bool velocityChange = false)
+        {
+            Vector3 j = transform.InverseTransformVector(impulse);
+            Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_SURFACE, flags = velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u,
+                                  index = hit.triangle, u = hit.barycentric.y, v = hit.barycentric.z, vecX = j.x, vecY = j.y, vecZ = j.z });
+        }
+
+        /// <summary>Rigidbody.AddExplosionForce as an impulse, for every particle within radius of the world-space centre, on the positions the
+        /// last tick ended with; linearFalloff: full strength at the centre, none at the radius (Unity's behaviour); negative strength pulls
+        /// inwards. The radius is taken in the component's local space.</summary>
+        public void AddExplosionImpulse(float strength, Vector3 centre, float radius, bool linearFalloff = true, bool velocityChange = false)
+        {
+            Vector3 c = transform.InverseTransformPoint(centre);
+            Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_RADIAL,
+                                  flags = (linearFalloff ? SoftbodyNative.SB_IMPULSE_LINEAR_FALLOFF : 0u) | (velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u),
+                                  vecX = c.x, vecY = c.y, vecZ = c.z, radius = radius, strength = strength });
+        }
+
+        void Queue(SbImpulse item)
+        {
+            if (impulseCount == impulseQueue.Length) Array.Resize(ref impulseQueue, 2 * impulseQueue.Length);
+            impulseQueue[impulseCount++] = item;
+        }
+
+        void SendImpulses()
+        {
+            if (impulseCount == 0) return;
+            int count = impulseCount;
+            impulseCount = 0;                                // (an error drops the batch instead of repeating it every tick)
+            if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_impulses(handle, impulseQueue, count), "sb_group_apply_impulses");
+            else if (cpu != null) cpu.ApplyImpulses(impulseQueue, count, renderTriangles);
         }
 
         /// <summary>Attachments: move pinned particles (inverse mass 0) to new positions before the next FixedUpdate; their constrained

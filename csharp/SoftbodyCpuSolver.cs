@@ -87,6 +87,78 @@ namespace SoftbodyMI355X
             }
         }
 
+        // SPEC.md 2c: impulses between two ticks, items in list order, velocities only. SURFACE items act against `tri` (particle indices:
+        // the CPU branch has no embedding); the validation is the plugin's (softbody.h), here as exceptions before anything is applied.
+        public void ApplyImpulses(SbImpulse[] items, int count, int[] tri)
+        {
+            Vector3[] x = sb.positions; Vector3[] v = sb.velocities; float[] w = sb.inverseMass;
+            int n = x.Length, m = tri != null ? tri.Length / 3 : 0;
+            for (int i = 0; i < count; ++i)
+            {
+                SbImpulse it = items[i];
+                bool radial = it.kind == SoftbodyNative.SB_IMPULSE_RADIAL;
+                if (it.kind < 0 || it.kind > 2 || (it.flags & ~3u) != 0 || it.reserved0 != 0 || it.reserved1 != 0) throw new ArgumentException("impulse: unknown kind or flag bit, or reserved not 0");
+                if ((it.flags & SoftbodyNative.SB_IMPULSE_LINEAR_FALLOFF) != 0 && !radial) throw new ArgumentException("impulse: linear falloff on a non-radial item");
+                if (!Finite(it.vecX) || !Finite(it.vecY) || !Finite(it.vecZ)) throw new ArgumentException("impulse: NaN or infinite vec");
+                if (it.kind == SoftbodyNative.SB_IMPULSE_PARTICLE && (it.index < 0 || it.index >= n)) throw new ArgumentException("impulse: particle index out of range");
+                if (it.kind == SoftbodyNative.SB_IMPULSE_SURFACE)
+                {
+                    if (m == 0) throw new InvalidOperationException("impulse: a SURFACE item while no triangle list is in force");
+                    if (it.index < -1 || it.index >= m) throw new ArgumentException("impulse: triangle index out of range");
+                    if (it.index >= 0 && (!Finite(it.u) || !Finite(it.v))) throw new ArgumentException("impulse: NaN or infinite barycentric coordinate");
+                }
+                if (radial && (!(it.radius > 0f) || !Finite(it.strength))) throw new ArgumentException("impulse: radius must be positive, strength finite");
+            }
+            for (int i = 0; i < count; ++i)
+            {
+                SbImpulse it = items[i];
+                bool vc = (it.flags & SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE) != 0;
+                if (it.kind == SoftbodyNative.SB_IMPULSE_PARTICLE) Entry(v, w, it.index, it.vecX, it.vecY, it.vecZ, vc);
+                else if (it.kind == SoftbodyNative.SB_IMPULSE_SURFACE)
+                {
+                    if (it.index < 0) continue;
+                    float b0 = (float)(1.0f - it.u); b0 = (float)(b0 - it.v);
+                    Entry(v, w, tri[3 * it.index], (float)(b0 * it.vecX), (float)(b0 * it.vecY), (float)(b0 * it.vecZ), vc);
+                    Entry(v, w, tri[3 * it.index + 1], (float)(it.u * it.vecX), (float)(it.u * it.vecY), (float)(it.u * it.vecZ), vc);
+                    Entry(v, w, tri[3 * it.index + 2], (float)(it.v * it.vecX), (float)(it.v * it.vecY), (float)(it.v * it.vecZ), vc);
+                }
+                else
+                {
+                    float R2 = (float)(it.radius * it.radius);
+                    bool falloff = (it.flags & SoftbodyNative.SB_IMPULSE_LINEAR_FALLOFF) != 0;
+                    for (int p = 0; p < n; ++p)
+                    {
+                        float dx = (float)(x[p].x - it.vecX), dy = (float)(x[p].y - it.vecY), dz = (float)(x[p].z - it.vecZ);
+                        float xx = (float)(dx * dx), yy = (float)(dy * dy), zz = (float)(dz * dz);
+                        float r2 = (float)((float)(xx + yy) + zz);
+                        if (!(w[p] > 0f && 0f < r2 && r2 <= R2 && r2 < float.PositiveInfinity)) continue;      // NaN compares false; the centre has no direction
+                        float r = (float)Math.Sqrt(r2);      // (the double root of a float, rounded once more, is the correctly rounded float root)
+                        float f = it.strength;
+                        if (falloff) { float q = (float)(r / it.radius); float g = (float)(1.0f - q); f = (float)(it.strength * g); }
+                        float we = vc ? 1.0f : w[p];
+                        float s = (float)(we * f);
+                        float nx = (float)(dx / r), ny = (float)(dy / r), nz = (float)(dz / r);
+                        float ax = (float)(s * nx), ay = (float)(s * ny), az = (float)(s * nz);
+                        v[p] = new Vector3(Canonical((float)(v[p].x + ax)), Canonical((float)(v[p].y + ay)), Canonical((float)(v[p].z + az)));
+                    }
+                }
+            }
+        }
+
+        static bool Finite(float f) { return !(float.IsNaN(f) || float.IsInfinity(f)); }
+
+        // v_p.c = v_p.c + (we_p * G.c); a pinned particle is skipped
+        static void Entry(Vector3[] v, float[] w, int p, float gx, float gy, float gz, bool velocityChange)
+        {
+            if (w[p] == 0f) return;
+            float we = velocityChange ? 1.0f : w[p];
+            float ax = (float)(we * gx), ay = (float)(we * gy), az = (float)(we * gz);
+            v[p] = new Vector3(Canonical((float)(v[p].x + ax)), Canonical((float)(v[p].y + ay)), Canonical((float)(v[p].z + az)));
+        }
+
+        // SPEC.md 2c: a NaN that comes out of an impulse's addition is the canonical quiet NaN 0x7fc00000
+        static float Canonical(float f) { return float.IsNaN(f) ? BitConverter.ToSingle(BitConverter.GetBytes(0x7fc00000), 0) : f; }
+
         // SPEC.md §4
         static void ProjectDistance(Vector3[] x, float[] w, int i, int j, float L0, float at)
         {

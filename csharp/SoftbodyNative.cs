@@ -122,6 +122,21 @@ namespace SoftbodyMI355X
         public float t, u, v;
     }
 
+    /// <summary>sb_impulse (48 bytes): one item of sb_apply_impulses / sb_group_apply_impulses (SPEC.md 2c). kind = SoftbodyNative.SB_IMPULSE_PARTICLE / _SURFACE / _RADIAL, flags = SB_IMPULSE_VELOCITY_CHANGE | SB_IMPULSE_LINEAR_FALLOFF;
+    /// PARTICLE: index = particle, vec = J; SURFACE: index = triangle (-1 skips the item), (u, v) as SbRayHit gives them, vec = J;
+    /// RADIAL: vec = centre, radius, strength. reserved stays 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbImpulse
+    {
+        public int kind;
+        public uint flags;
+        public int index;
+        public float u, v;
+        public float vecX, vecY, vecZ;
+        public float radius, strength;
+        public int reserved0, reserved1;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -141,6 +156,9 @@ namespace SoftbodyMI355X
         public const int ScheduleAuto = 0, ScheduleSerialEager = 1, ScheduleSerialGraph = 2, ScheduleOverlapEager = 3, ScheduleOverlapGraph = 4;
         public const uint GroupWalk = 1;       // sb_group_create flags: no plugin threads, the calling thread walks the tick across the ranks
         public const uint GroupWholeMesh = 2;  // never cut windows: every rank plans the whole mesh (sb_group_finalize)
+        // sb_impulse (SPEC.md 2c), named as in include/softbody.h
+        public const int SB_IMPULSE_PARTICLE = 0, SB_IMPULSE_SURFACE = 1, SB_IMPULSE_RADIAL = 2;      // SbImpulse.kind
+        public const uint SB_IMPULSE_VELOCITY_CHANGE = 1, SB_IMPULSE_LINEAR_FALLOFF = 2;               // SbImpulse.flags (LINEAR_FALLOFF: RADIAL only)
 
         [DllImport(Lib, CallingConvention = CC)] public static extern void sb_desc_default(ref SbDesc d);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_create(ref SbDesc desc, out IntPtr solver);
@@ -163,6 +181,8 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_state(IntPtr s, IntPtr posXyz, IntPtr velXyz, int n);
         // kinematic particles (attachments): move particles with inverse mass 0 between two ticks (SPEC.md 2); a rank applies the ones it owns
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_kinematic_positions(IntPtr s, IntPtr ids, IntPtr posXyz, int count);
+        // impulses between two ticks (SPEC.md 2c): velocities only; the next sb_step starts unfused
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_apply_impulses(IntPtr s, SbImpulse[] items, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_begin(IntPtr s);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_readback_end(IntPtr s, out IntPtr posXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_set_render_triangles(IntPtr s, int[] triAbc, int m);
@@ -229,6 +249,7 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_velocities(IntPtr g, IntPtr velXyzOut, int n);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_state(IntPtr g, IntPtr posXyz, IntPtr velXyz, int n);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_kinematic_positions(IntPtr g, IntPtr ids, IntPtr posXyz, int count);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_apply_impulses(IntPtr g, SbImpulse[] items, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_triangles(IntPtr g, int[] triAbc, int m);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_embedding(IntPtr g, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_uvs(IntPtr g, IntPtr uv, int count);

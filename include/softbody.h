@@ -21,7 +21,7 @@
  *    SB_ERR_NO_DEVICE.
  *  - Semantics of one tick: SPEC.md.
  *
- * This header is the whole PRODUCT surface of a solver handle (39 functions). Beside it:
+ * This header is the whole PRODUCT surface of a solver handle (40 functions). Beside it:
  *   softbody_group.h  one process -- a Unity player -- driving several GPUs behind the same component (sb_group_*)
  *   softbody_plan.h   host-only planner inspection (published order, tiles, halo lists; frame / window of sharded authoring)
  *   softbody_debug.h  test hooks, the table validator, per-launch timing and the tuning switches of A/B measurements
@@ -190,6 +190,46 @@ int sb_set_state(sb_solver *s, const float *pos_xyz, const float *vel_xyz, int32
  * (world > 1) is given the same list in its own numbering (the whole list on every rank is fine): every entry is validated, the rank applies
  * the particles it OWNS and skips the others -- their owners apply them, and the ghost copies arrive with the next exchange. */
 int sb_set_kinematic_positions(sb_solver *s, const int32_t *ids, const float *pos_xyz, int32_t count);
+/* Impulses between two ticks (SPEC.md 2c; what Unity's Rigidbody.AddForce(ForceMode.Impulse / VelocityChange), AddForceAtPosition and
+ * AddExplosionForce are to a rigid body): a click, a bullet, a footstep, an explosion. count items, applied in list order (calls in call
+ * order); an item changes VELOCITIES only, of particles with a non-zero inverse mass (a pinned particle is skipped silently: a hit may land
+ * on one), in binary32 without FMA:
+ *  - SB_IMPULSE_PARTICLE: v[index] += we * vec, we = the particle's inverse mass (vec is an impulse), or 1 with SB_IMPULSE_VELOCITY_CHANGE
+ *    (vec is a velocity change). The same id may occur any number of times.
+ *  - SB_IMPULSE_SURFACE: vec at the point (u, v) of triangle `index` of the render mode in force -- copy triangle, u, v straight out of an
+ *    sb_ray_hit, misses included (index = -1 skips the item). With render triangles the corners a, b, c take (1 - u - v, u, v) times vec;
+ *    with an embedding every corner's share goes on to its four cage particles times the skinning weights (the transpose of SPEC.md 6b),
+ *    twelve entries per item.
+ *  - SB_IMPULSE_RADIAL: an explosion at centre vec on the tick-end positions: every particle with 0 < |x - centre|^2 <= radius^2 gets
+ *    we * f along (x - centre) / |x - centre|, f = strength, or strength * (1 - |x - centre| / radius) with SB_IMPULSE_LINEAR_FALLOFF.
+ *    Negative strength pulls inwards; radius = +inf is allowed.
+ * The whole list is validated before anything is applied; on an error nothing changes. SB_ERR_INVALID_ARG: a null handle, null items with
+ * count > 0, count < 0, an unknown kind or flag bit, LINEAR_FALLOFF on a non-radial item, non-zero reserved, a PARTICLE index outside
+ * [0, n), a SURFACE index outside [-1, m), a NaN or infinite vec, a NaN or infinite u or v of a SURFACE item with index >= 0, a radius that
+ * is NaN or <= 0, a NaN or infinite strength (fields a kind does not use are not looked at). SB_ERR_STATE: before sb_finalize; a SURFACE
+ * item while no triangle list is in force (neither render triangles, nor an embedding with m_tri > 0). count = 0 returns SB_OK.
+ * Asynchronous like sb_step (the items are copied before the call returns; kernels on the solver's stream). Velocities exist only once a
+ * tick is complete, so the call completes the tick's held-back last kernel (and lands pending kinematic targets, as every state write
+ * does): THE NEXT sb_step STARTS UNFUSED -- sb_stats.ticks_fused does not rise for it, and rises again for the steps after it.
+ * A rank of a partitioned solver (world > 1) takes PARTICLE and RADIAL items in its own numbering (the whole list on every rank is fine):
+ * it validates every item and applies them to the particles it OWNS. A SURFACE item there returns SB_ERR_UNSUPPORTED, for the reason
+ * sb_readback_raycast does (sb_group_apply_impulses serves that case). Nothing is allocated before the first call.
+ * A velocity component that comes out of an item's addition as NaN is stored as the quiet NaN 0x7fc00000 (SPEC.md 2c). */
+#define SB_IMPULSE_PARTICLE 0
+#define SB_IMPULSE_SURFACE  1
+#define SB_IMPULSE_RADIAL   2
+#define SB_IMPULSE_VELOCITY_CHANGE 1u   /* flags: the vector is a velocity change, not an impulse (Unity ForceMode.VelocityChange) */
+#define SB_IMPULSE_LINEAR_FALLOFF  2u   /* flags, RADIAL only */
+typedef struct {                 /* 48 bytes */
+    int32_t  kind;
+    uint32_t flags;
+    int32_t  index;              /* PARTICLE: particle id; SURFACE: triangle, -1 = skip this item; RADIAL: ignored */
+    float    u, v;               /* SURFACE: barycentric coordinates as sb_ray_hit gives them */
+    float    vec[3];             /* PARTICLE, SURFACE: J; RADIAL: centre */
+    float    radius, strength;   /* RADIAL */
+    int32_t  reserved[2];        /* must be 0 */
+} sb_impulse;
+int sb_apply_impulses(sb_solver *s, const sb_impulse *items, int32_t count);
 /* Asynchronous render readback: sb_readback_begin snapshots the positions as of every sb_step issued so far
  * (a small kernel on the compute stream) and starts a D2H copy into plugin-owned pinned memory on a second
  * stream; the next sb_step overlaps with that copy. sb_readback_end waits for the OLDEST pending snapshot and

@@ -87,6 +87,11 @@ int sb_group_get_velocities(sb_group *g, float *vel_xyz_out, int32_t n);
 int sb_group_set_state(sb_group *g, const float *pos_xyz, const float *vel_xyz, int32_t n);
 /* Kinematic targets (sb_set_kinematic_positions): ids in the caller's numbering, each at most once; every rank takes the ones it owns. */
 int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const float *pos_xyz, int32_t count);
+/* Impulses between two ticks (sb_apply_impulses, SPEC.md 2c), same contract, in the whole mesh's numbering: the list is validated once,
+ * SURFACE items are expanded on the host from the group's own copies of the triangles and the embedding (a cage may straddle ranks),
+ * every rank is handed its entries in order and in its numbering, RADIAL items go to every rank unchanged. Every rank completes its
+ * tick's held-back last kernel, so the ranks stay in the same tick state. Both host models. */
+int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count);
 
 /* ---- render readback (same contract as sb_readback_* / sb_set_render_triangles of softbody.h) -------------------------------------------- */
 /* Every rank snapshots the particles it owns (peeking while its tick's last kernel is held back) straight into ONE buffer on the render device

@@ -621,6 +621,30 @@ int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const floa
     });
 }
 
+int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count) {
+    if (!g || count < 0 || (count > 0 && !items)) return fail(SB_ERR_INVALID_ARG, "sb_group_apply_impulses: bad argument (null handle, null items or negative count)");
+    if (int rc = check_group(g, true, "sb_group_apply_impulses")) return rc;
+    if (count == 0) return SB_OK;
+    return guarded([&]() -> int {
+        if (int rc = validate_impulses("sb_group_apply_impulses", items, count, g->n, impulse_triangles_in_force(g->render), false)) return rc;
+        // SURFACE items expanded here (a triangle's particles, a vertex' cage, may belong to several ranks), then every rank its entries in
+        // list order and in its own numbering; an explosion reaches the particles of every rank
+        std::vector<sb_impulse> flat;
+        expand_impulses(g->render, items, count, flat);
+        std::vector<std::vector<sb_impulse>> per_rank((size_t)g->W);
+        for (const sb_impulse &it : flat) {
+            if (it.kind == SB_IMPULSE_RADIAL) { for (auto &v : per_rank) v.push_back(it); continue; }
+            sb_impulse e = it;
+            e.index = g->index_in_rank[(size_t)it.index];
+            per_rank[(size_t)g->owner[(size_t)it.index]].push_back(e);
+        }
+        // (a rank with nothing to apply still completes its tick: the ranks stay in the same tick state, as under sb_group_set_state)
+        return g->for_ranks([&](int r) {
+            return guarded([&]() -> int { return apply_impulses_validated(g->ranks[(size_t)r], per_rank[(size_t)r].data(), (int32_t)per_rank[(size_t)r].size()); });
+        });
+    });
+}
+
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */
 
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {

@@ -3,7 +3,7 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
-// tick), readback.hip (state reads / writes, kinematic targets), render.hip (render readback: the stage and the entry-point bodies a solver
+// tick), readback.hip (state reads / writes, kinematic targets), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
@@ -299,6 +299,14 @@ struct sb_solver {
     DevBuf<float> d_kin_target;            // 3 floats per pinned particle: pending target or NaN
     int64_t n_kin_fused = 0;               // ticks whose fused first kernel carried targets
     bool kin_fuse = true;                  // !SB_TUNE_NO_KIN_FUSE (A/B: pending targets always complete the previous tick first)
+    // impulses (sb_apply_impulses, impulse.hip): the sparse kernel's tables travel like the kinematic targets -- a ring of mapped pinned
+    // buffers, each reused only after the kernel that read it has finished (its event); allocated at the first call
+    static constexpr int kImpSlots = 4;
+    void *h_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};
+    void *d_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};         // device-side aliases of the mapped tables
+    size_t imp_cap[kImpSlots] = {0, 0, 0, 0};                              // bytes
+    hipEvent_t ev_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};
+    int imp_next = 0;
     // Peek (world == 1): a position read while the tick's last kernel is deferred runs tile_kernel<4> -- the same rounds + collide on
     // the same inputs, written to d_peek instead of the state -- so the deferred kernel can still be fused with the next tick's first
     // one. A render-set-only readback peeks only at the T0 tiles that hold a render particle (peek_tiles: copies of their descriptors).
@@ -343,6 +351,10 @@ struct sb_solver {
             if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
             if (h_kin_pos[k]) (void)hipHostFree(h_kin_pos[k]);
             if (ev_kin[k]) (void)hipEventDestroy(ev_kin[k]);
+        }
+        for (int k = 0; k < kImpSlots; ++k) {
+            if (h_imp[k]) (void)hipHostFree(h_imp[k]);
+            if (ev_imp[k]) (void)hipEventDestroy(ev_imp[k]);
         }
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -391,6 +403,12 @@ int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t co
 const float *render_source(sb_solver *s, bool compact, const std::vector<int32_t> &wanted_local);
 // sb_get_bounds: the box of the particles this rank owns, on what sb_get_positions would return now (peeks where that peeks)
 int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]);
+
+// ---- impulse.hip: impulses between two ticks (SPEC.md 2c) ----------------------------------------------------------------------------------
+int64_t impulse_triangles_in_force(const RenderState &R);       // triangles of the render mode in force, -1 = none
+int validate_impulses(const char *who, const sb_impulse *items, int32_t count, int32_t n, int64_t m_tri, bool rank);
+void expand_impulses(const RenderState &R, const sb_impulse *items, int32_t count, std::vector<sb_impulse> &out);      // SURFACE -> PARTICLE-like entries
+int apply_impulses_validated(sb_solver *s, const sb_impulse *items, int32_t count);      // PARTICLE / RADIAL, the rank's numbering, owned particles
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

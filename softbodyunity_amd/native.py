@@ -29,6 +29,8 @@ SB_GROUP_WHOLE_MESH = 2
 (SB_TUNE_NO_MASS_PALETTE, SB_TUNE_NO_UNIFORM_MASS, SB_TUNE_NO_PALETTE, SB_TUNE_NO_WAVE_ITEMS, SB_TUNE_NO_LANE_PACK, SB_TUNE_NO_COST_ORDER,
  SB_TUNE_NO_FUSED_UNPACK, SB_TUNE_PEER_COARSE, SB_TUNE_NO_LAZY_TICK, SB_TUNE_NO_PACK, SB_TUNE_NO_PEEK, SB_TUNE_NO_KIN_FUSE,
  SB_TUNE_NO_WIDE_SLOTS, SB_TUNE_AUTO_PREFER_OVERLAP, SB_TUNE_NO_AUTO_CALIBRATION, SB_TUNE_NO_SHARED_PROGRAMS) = (1 << k for k in range(16))
+SB_IMPULSE_PARTICLE, SB_IMPULSE_SURFACE, SB_IMPULSE_RADIAL = 0, 1, 2
+SB_IMPULSE_VELOCITY_CHANGE, SB_IMPULSE_LINEAR_FALLOFF = 1, 2
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -104,6 +106,12 @@ class SbRayHit(C.Structure):
     _fields_ = [("triangle", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
 
 
+class SbImpulse(C.Structure):
+    """sb_impulse (48 bytes): one item of sb_apply_impulses (SPEC.md 2c)"""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_uint32), ("index", C.c_int32), ("u", C.c_float), ("v", C.c_float),
+                ("vec", C.c_float * 3), ("radius", C.c_float), ("strength", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -129,6 +137,7 @@ SIGNATURES = {
     "sb_get_velocities": (C.c_int, [_P, _P, C.c_int32]),
     "sb_set_kinematic_positions": (C.c_int, [_P, _P, _P, C.c_int32]),
     "sb_set_state": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "sb_apply_impulses": (C.c_int, [_P, C.POINTER(SbImpulse), C.c_int32]),
     "sb_readback_begin": (C.c_int, [_P]),
     "sb_readback_end": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float))]),
     "sb_set_render_triangles": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
@@ -193,6 +202,7 @@ SIGNATURES = {
     "sb_group_get_velocities": (C.c_int, [_P, _P, C.c_int32]),
     "sb_group_set_state": (C.c_int, [_P, _P, _P, C.c_int32]),
     "sb_group_set_kinematic_positions": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "sb_group_apply_impulses": (C.c_int, [_P, C.POINTER(SbImpulse), C.c_int32]),
     "sb_group_set_render_triangles": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "sb_group_set_render_embedding": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "sb_group_set_render_uvs": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),

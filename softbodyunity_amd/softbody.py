@@ -260,6 +260,11 @@ class Softbody:
         pos = f32(pos, (-1, 3)); vel = f32(vel, (-1, 3))
         check(native.lib().sb_set_state(self._h, ptr(pos), ptr(vel), self.n))
 
+    def apply_impulses(self, items):
+        """Impulses between two ticks (SPEC.md 2c): items = an IMPULSE structured array, or a list of such arrays (impulse_particles,
+        impulse_hits, impulse_explosion), applied in order. Velocities change, positions do not; the next step starts unfused."""
+        _apply_impulses(native.lib().sb_apply_impulses, self._h, items)
+
     def owner(self):
         out = np.zeros(self.n, np.int32)
         check(native.lib().sb_get_owner(self._h, ptr(out), self.n))
@@ -344,6 +349,51 @@ def _raycast(fn, handle, rays):
     hits = np.zeros(rays.shape[0], RAY_HIT)
     check(fn(handle, _fp(rays), rays.shape[0], hits.ctypes.data_as(C.POINTER(native.SbRayHit))))
     return hits
+
+
+# sb_impulse as a numpy record (48 bytes, the layout of native.SbImpulse)
+IMPULSE = np.dtype([("kind", np.int32), ("flags", np.uint32), ("index", np.int32), ("u", np.float32), ("v", np.float32),
+                    ("vec", np.float32, (3,)), ("radius", np.float32), ("strength", np.float32), ("reserved", np.int32, (2,))])
+
+
+def impulse_particles(ids, vec, velocity_change=False):
+    """PARTICLE items: impulse (or, with velocity_change, velocity change) vec -- (3,) for all, or (K, 3) -- on particles ids."""
+    ids = np.atleast_1d(np.asarray(ids, np.int32))
+    out = np.zeros(ids.shape[0], IMPULSE)
+    out["kind"] = native.SB_IMPULSE_PARTICLE
+    out["flags"] = native.SB_IMPULSE_VELOCITY_CHANGE if velocity_change else 0
+    out["index"] = ids
+    out["vec"] = np.asarray(vec, np.float32)
+    return out
+
+
+def impulse_hits(hits, vec, velocity_change=False):
+    """SURFACE items from the structured array raycast() returns, misses included (they are skipped): vec -- (3,) or (R, 3) -- at every hit."""
+    hits = np.atleast_1d(hits)
+    out = np.zeros(hits.shape[0], IMPULSE)
+    out["kind"] = native.SB_IMPULSE_SURFACE
+    out["flags"] = native.SB_IMPULSE_VELOCITY_CHANGE if velocity_change else 0
+    out["index"] = hits["triangle"]; out["u"] = hits["u"]; out["v"] = hits["v"]
+    out["vec"] = np.asarray(vec, np.float32)
+    return out
+
+
+def impulse_explosion(centre, radius, strength, linear_falloff=False, velocity_change=False):
+    """One RADIAL item (Unity's AddExplosionForce as an impulse); negative strength pulls inwards, radius may be inf."""
+    out = np.zeros(1, IMPULSE)
+    out["kind"] = native.SB_IMPULSE_RADIAL
+    out["flags"] = (native.SB_IMPULSE_LINEAR_FALLOFF if linear_falloff else 0) | (native.SB_IMPULSE_VELOCITY_CHANGE if velocity_change else 0)
+    out["vec"] = np.asarray(centre, np.float32)
+    out["radius"] = radius; out["strength"] = strength
+    return out
+
+
+def _apply_impulses(fn, handle, items):
+    """one of the *_apply_impulses entry points on an IMPULSE array or a list of them"""
+    if isinstance(items, (list, tuple)):
+        items = np.concatenate([np.atleast_1d(np.asarray(a, IMPULSE)) for a in items]) if len(items) else np.zeros(0, IMPULSE)
+    items = np.ascontiguousarray(items, dtype=IMPULSE)
+    check(fn(handle, items.ctypes.data_as(C.POINTER(native.SbImpulse)), int(items.shape[0])))
 
 
 def _uv_args(uv):
@@ -478,6 +528,10 @@ class SoftbodyGroup:
         ids = i32(ids); pos = f32(pos, (-1, 3))
         assert pos.shape[0] == ids.shape[0]
         check(native.lib().sb_group_set_kinematic_positions(self._g, ptr(ids), ptr(pos), int(ids.shape[0])))
+
+    def apply_impulses(self, items):
+        """Softbody.apply_impulses in the whole mesh's numbering; SURFACE items against the group's triangles / embedding."""
+        _apply_impulses(native.lib().sb_group_apply_impulses, self._g, items)
 
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
