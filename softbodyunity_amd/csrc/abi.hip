@@ -46,9 +46,9 @@ int sb_create(const sb_desc *desc, sb_solver **out) {
         s->desc = d;
         s->peer.enabled = d.world > 1 && d.halo_transport == SB_TRANSPORT_PEER;
         s->loopback = d.world > 1 && (d.debug_flags & SB_DEBUG_LOOPBACK) != 0;
-        HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreate(&s->ev0));
-        HIP_CHECK(hipEventCreate(&s->ev1));
+        s->stream.create();
+        s->ev0.create();
+        s->ev1.create();
         *out = s.release();
         return SB_OK;
     });
@@ -362,9 +362,9 @@ int finalize_device(sb_solver *s) {
         // (an ordinary stream: a highest-priority one -- meant to keep the pack kernel and RCCL's few workgroups from queueing behind
         // the interior launch -- made the eager overlapped tick FOUR TIMES slower on this runtime, 0.93 -> 3.35 ms in the W = 8
         // loopback, profiles/r03r_loopback_w8_priority_stream_not_kept.txt)
-        HIP_CHECK(hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&s->ev_boundary, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&s->ev_halo, hipEventDisableTiming));
+        s->comm_stream.create();
+        s->ev_boundary.create(hipEventDisableTiming);
+        s->ev_halo.create(hipEventDisableTiming);
     }
     return SB_OK;
 }

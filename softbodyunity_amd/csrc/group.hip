@@ -110,7 +110,7 @@ struct sb_group {
         DevBuf<int32_t> d_target_of_local;       // owned particle l -> caller id (full snapshots)
         DevBuf<int32_t> d_rs_ids, d_rs_local;    // the render particles (or, with an embedding, the cage particles) the rank owns: caller id, device index
         std::vector<int32_t> rs_local;
-        hipEvent_t ev_snap[kSnapSlots] = {nullptr, nullptr, nullptr};
+        Event ev_snap[kSnapSlots];
         int64_t acct = 0;
     };
     std::vector<RankRender> rr;
@@ -123,23 +123,24 @@ struct sb_group {
         for (int r = 0; r < W; ++r) { const int rc = f(r); if (rc) return fail(rc, "rank " + std::to_string(r) + ": " + last_error_text()); }
         return SB_OK;
     }
+    // The destructor holds only what is ORDER (and which device is current); the handles give themselves back.
     ~sb_group() {
+        // 1. the rank threads are joined: nobody else drives a device from here on
         threads.reset();
-        if (!ranks.empty()) {
-            // every rank quiescent before any mailbox / buffer a neighbour writes into goes away
-            for (sb_solver *s : ranks) if (s && s->finalized) (void)sb_synchronize(s);
-        }
+        // 2. EVERY rank quiescent before ANY rank, mailbox or gather buffer goes away: neighbours push into each other's mailboxes and the
+        //    snapshot kernels of every rank write into the render device's gather buffers
+        for (sb_solver *s : ranks) if (s && s->finalized) (void)sb_synchronize(s);
+        // 3. the render copy stream drained before its buffers go
         if (!devices.empty()) (void)hipSetDevice(devices[0]);
         if (render.copy_stream) (void)hipStreamSynchronize(render.copy_stream);
-        for (hipEvent_t e : render.ev_copied) if (e) (void)hipEventDestroy(e);
-        render.release();
-        if (render.copy_stream) (void)hipStreamDestroy(render.copy_stream);
+        // 4. every resource is destroyed with its own device current: the per-rank entries here, one device after the other, ...
         for (size_t r = 0; r < rr.size(); ++r) {
             (void)hipSetDevice(devices[r]);
-            for (int k = 0; k < kSnapSlots; ++k) if (rr[r].ev_snap[k]) (void)hipEventDestroy(rr[r].ev_snap[k]);
-            rr[r].d_target_of_local.free(); rr[r].d_rs_ids.free(); rr[r].d_rs_local.free();
+            rr[r] = RankRender{};
         }
-        for (sb_solver *s : ranks) if (s) (void)sb_destroy(s);
+        for (sb_solver *s : ranks) if (s) (void)sb_destroy(s);       // (sets the rank's device itself)
+        // ... and `render`, a member that dies after this body, on the render device: so that device is the body's last word
+        if (!devices.empty()) (void)hipSetDevice(devices[0]);
     }
 };
 
@@ -718,7 +719,7 @@ int gather_snapshots(sb_group *g, int k, bool subset) {
             sb_solver *s = g->ranks[(size_t)r];
             int rcd = set_device(s); if (rcd) return rcd;
             auto &Q = g->rr[(size_t)r];
-            const float *src = render_source(s, subset, Q.rs_local);
+            const float *src = tick_end_positions(s, subset, Q.rs_local);
             if (subset) launch_snapshot_subset(s, src, Q.d_rs_ids.p, Q.d_rs_local.p, (int)Q.rs_local.size(), dst);
             else launch_snapshot_all(s, src, Q.d_target_of_local.p, dst);
             HIP_CHECK(hipEventRecord(Q.ev_snap[k], s->stream));
@@ -743,13 +744,14 @@ int sb_group_readback_begin(sb_group *g) {
         const int W = g->W, dev0 = g->device_of(0);
         const size_t n3 = (size_t)g->n * 3;
         HIP_CHECK(hipSetDevice(dev0));
-        if (!R.copy_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&R.copy_stream, hipStreamNonBlocking));
+        // first use, keyed on what it creates last (the last rank's last event); every step before it can simply be done again
+        if (g->rr.empty() || !g->rr.back().ev_snap[kSnapSlots - 1]) {
+            R.copy_stream.create();
             g->rr.resize((size_t)W);
             for (int k = 0; k < kSnapSlots; ++k) {
                 R.pos[k].d.alloc(n3, g->dev_bytes);       // (its pinned twin: with the first full snapshot of the slot)
                 HIP_CHECK(hipMemset(R.pos[k].d.p, 0, n3 * sizeof(float)));
-                HIP_CHECK(hipEventCreateWithFlags(&R.ev_copied[k], hipEventDisableTiming));
+                R.ev_copied[k].create(hipEventDisableTiming);
             }
             for (int r = 0; r < W; ++r) {      // owned particle -> caller id, on the rank's device
                 sb_solver *s = g->ranks[(size_t)r];
@@ -759,7 +761,7 @@ int sb_group_readback_begin(sb_group *g) {
                 std::vector<int32_t> target((size_t)s->n_owned);
                 for (int64_t l = 0; l < s->n_owned; ++l) { const int32_t o = L.local_to_old[(size_t)l]; target[(size_t)l] = map ? map[o] : o; }
                 g->rr[(size_t)r].d_target_of_local.upload(target, g->rr[(size_t)r].acct);
-                for (int k = 0; k < kSnapSlots; ++k) HIP_CHECK(hipEventCreateWithFlags(&g->rr[(size_t)r].ev_snap[k], hipEventDisableTiming));
+                for (int k = 0; k < kSnapSlots; ++k) g->rr[(size_t)r].ev_snap[k].create(hipEventDisableTiming);
             }
             HIP_CHECK(hipSetDevice(dev0));
         }
@@ -790,8 +792,8 @@ int sb_group_readback_begin(sb_group *g) {
                     cage[(size_t)v] = make_int4(c[0], c[1], c[2], c[3]);
                     for (int j = 0; j < 4; ++j) if (!seen[(size_t)c[j]]) { seen[(size_t)c[j]] = 1; distinct.push_back(c[j]); }
                 }
-                E.upload(cage, g->dev_bytes);
                 upload_rank_subsets(g, distinct);
+                E.upload(cage, g->dev_bytes);      // (last: it clears E.dirty, the key of this block)
             }
             if (int rc = gather_snapshots(g, k, /*subset=*/true)) return rc;
             launch_skin(R.copy_stream, R.pos[k].d.p, E.d_cage.p, E.d_w.p, E.pos[k].d.p, (int)E.m);
@@ -802,7 +804,7 @@ int sb_group_readback_begin(sb_group *g) {
         } else {
             const int count = compact ? (int)R.set.size() : (int)g->n;
             // this slot's buffers, by what it will carry (they only grow)
-            if (!compact && !R.pos[k].h) R.pos[k].pin();
+            if (!compact && !R.pos[k].h.p) R.pos[k].pin();
             if (!R.tri.empty()) {
                 if (R.nrm[k].d.count < (size_t)count * 3) R.nrm[k].alloc((size_t)count * 3, g->dev_bytes);
                 if (compact && R.cpos[k].d.count < (size_t)count * 3) R.cpos[k].alloc((size_t)count * 3, g->dev_bytes);

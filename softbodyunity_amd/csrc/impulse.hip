@@ -1,5 +1,5 @@
 // impulse.hip — impulses between two ticks (sb_apply_impulses, SPEC.md 2c): validation, the host-side expansion of SURFACE items, the
-// sort of sparse entries into per-particle runs, the table ring, and the launches. The group's entry point (group.hip) shares the
+// sort of sparse entries into per-particle runs, and the launches (the tables travel in a TableRing, device_handles.hpp). The group's entry point (group.hip) shares the
 // validation, the expansion and the rank path.
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported function is part of the
@@ -80,23 +80,6 @@ void expand_impulses(const RenderState &R, const sb_impulse *items, int32_t coun
 }
 
 namespace {
-
-// One call's table of the ring: mapped pinned memory the sparse kernels read in place; reused only after the last kernel that read it is done.
-void *ring_table(sb_solver *s, size_t bytes, int &slot) {
-    const int q = s->imp_next;
-    s->imp_next = (q + 1) % sb_solver::kImpSlots;
-    if (!s->ev_imp[q]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_imp[q], hipEventDisableTiming));
-    else HIP_CHECK(hipEventSynchronize(s->ev_imp[q]));       // (the call that used this table, four calls ago)
-    if (s->imp_cap[q] < bytes) {
-        if (s->h_imp[q]) { (void)hipHostFree(s->h_imp[q]); s->h_imp[q] = nullptr; s->imp_cap[q] = 0; }
-        const size_t cap = std::max<size_t>(4096, bytes * 2);
-        HIP_CHECK(hipHostMalloc(&s->h_imp[q], cap, hipHostMallocMapped));
-        HIP_CHECK(hipHostGetDevicePointer(&s->d_imp[q], s->h_imp[q], 0));
-        s->imp_cap[q] = cap;
-    }
-    slot = q;
-    return s->h_imp[q];
-}
 
 // The tables of one sparse run inside a call's table: [particle per lane][offsets, one more][pad to 16 bytes][float4 entries]
 struct SparseRun {
@@ -184,7 +167,8 @@ int apply_impulses_validated(sb_solver *s, const sb_impulse *items, int32_t coun
     }
     int q = -1;
     if (bytes) {
-        char *h = (char *)ring_table(s, bytes, q);
+        q = s->imp_ring.acquire(bytes);
+        char *h = s->imp_ring.host(q);
         for (const SparseRun &R : sparse) if (!R.mine.empty()) fill_sparse(R, items, h + R.at);
     }
     flush_deferred(s);
@@ -196,11 +180,11 @@ int apply_impulses_validated(sb_solver *s, const sb_impulse *items, int32_t coun
         if (radial) launch_radial(s, items + i, j - i);
         else {
             const SparseRun &R = sparse[next_sparse++];
-            if (!R.mine.empty()) launch_sparse(s, R, (const char *)s->d_imp[q] + R.at);
+            if (!R.mine.empty()) launch_sparse(s, R, s->imp_ring.device(q) + R.at);
         }
         i = j;
     }
-    if (q >= 0) HIP_CHECK(hipEventRecord(s->ev_imp[q], s->stream));
+    if (q >= 0) s->imp_ring.retire(q, s->stream);
     return SB_OK;
 }
 

@@ -1,4 +1,4 @@
-// readback.hip — state reads and writes, the bounding box of the state, kinematic targets, and where a render snapshot reads the tick-end positions (the readback itself: render.hip)
+// readback.hip — state reads and writes, the bounding box of the state, kinematic targets, and where the tick-end positions are for whoever reads them (the render readback itself: render.hip)
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
@@ -21,21 +21,40 @@ static void scatter_owned(const sb_solver *s, const float *staged, float *out, c
     });
 }
 
-// Positions (or velocities) of the particles this rank OWNS, written into `out` at their caller index (id_map: see scatter_owned);
-// entries of other ranks' particles are left alone. Position reads PEEK while the tick's last kernel is held back (the tick stays
-// fusable with the next one), on every rank of a partitioned solver too: the held-back kernel runs on T0 tiles, which hold owned
-// particles only and need no ghost.
+// Where the tick-end positions are, made valid on the solver's stream (synchronising is the caller's): while the tick's last kernel is held
+// back that is a PEEK into the side array -- every T0 tile, or (subset) only the tiles that hold a particle of `wanted_local`, a list built
+// once per render set -- with the pending kinematic targets scattered onto it (they show in what is read and stay pending); else the state
+// itself after the tick has been completed. The tick stays fusable with the next one after a peek, on every rank of a partitioned solver
+// too: the held-back kernel runs on T0 tiles, which hold owned particles only and need no ghost.
+const float *tick_end_positions(sb_solver *s, bool subset, const std::vector<int32_t> &wanted_local) {
+    if (!can_peek(s)) { flush_deferred(s); return s->d_pos3.p; }
+    if (subset && s->n_peek_tiles < 0) build_peek_subset(s, wanted_local);
+    peek_positions(s, subset);
+    if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p);
+    return s->d_peek.p;
+}
+
+// Positions (or velocities, which exist only once the tick is complete) of the particles this rank OWNS, written into `out` at their
+// caller index (id_map: see scatter_owned); entries of other ranks' particles are left alone.
 int get_state_owned(sb_solver *s, float *out, bool velocity, const int32_t *id_map) {
     int rc = set_device(s); if (rc) return rc;
-    const bool peek = !velocity && can_peek(s);
-    if (peek) { peek_positions(s, false); if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p); }     // (pending targets show in what is read; they stay pending)
-    else flush_deferred(s);
+    if (velocity) flush_deferred(s);
+    const float *src = velocity ? s->d_vel.p : tick_end_positions(s);
+    if (s->desc.world == 1) {
+        // single rank: every entry is ours, so the permutation to caller numbering runs on the GPU and one copy
+        // lands in the caller's array (a host-side scatter costs 25 ms for 16.7 M particles)
+        if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
+        if (!s->d_get_scratch.p) s->d_get_scratch.alloc((size_t)s->n * 3, s->dev_bytes);
+        launch_snapshot_all(s, src, s->d_local_to_old.p, s->d_get_scratch.p);
+        HIP_CHECK(hipMemcpyAsync(out, s->d_get_scratch.p, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        return SB_OK;
+    }
     HIP_CHECK(hipStreamSynchronize(s->stream));
     check_peer_error(s);
     s->h_stage.resize((size_t)s->n_owned * 3);
-    const float *src = velocity ? s->d_vel.p : (peek ? s->d_peek.p : s->d_pos3.p);
     if (s->n_owned) HIP_CHECK(hipMemcpy(s->h_stage.data(), src, (size_t)s->n_owned * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    scatter_owned(s, s->h_stage.data(), out, id_map);
+    scatter_owned(s, s->h_stage.data(), out, id_map);       // (world > 1: the caller merges the ranks' arrays)
     return SB_OK;
 }
 
@@ -45,23 +64,7 @@ static int get_state(sb_solver *s, float *out, int32_t n, bool velocity) {
     if (!s || !out) return fail(SB_ERR_INVALID_ARG, "sb_get_*: null argument");
     if (!s->finalized) return fail(SB_ERR_STATE, "sb_get_* before sb_finalize");
     if (n != s->n) return fail(SB_ERR_INVALID_ARG, "sb_get_*: n differs from sb_set_particles");
-    return guarded([&]() -> int {
-        if (s->desc.world != 1) return get_state_owned(s, out, velocity, nullptr);       // only the entries this rank owns (the caller merges the ranks' arrays)
-        int rc = set_device(s); if (rc) return rc;
-        const sbp::LocalPlan &L = s->plan->local;
-        // positions while the tick's last kernel is deferred: peek instead of completing the tick (the next sb_step keeps its fusion)
-        const bool peek = !velocity && can_peek(s);
-        if (peek) { peek_positions(s, false); if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p); }     // (pending targets show in what is read; they stay pending)
-        else flush_deferred(s);
-        // single rank: every entry is ours, so the permutation to caller numbering runs on the GPU and one copy
-        // lands in the caller's array (a host-side scatter costs 25 ms for 16.7 M particles)
-        if (!s->d_local_to_old.p) s->d_local_to_old.upload(L.local_to_old, s->dev_bytes);
-        if (!s->d_get_scratch.p) s->d_get_scratch.alloc((size_t)s->n * 3, s->dev_bytes);
-        launch_snapshot_all(s, velocity ? s->d_vel.p : (peek ? s->d_peek.p : s->d_pos3.p), s->d_local_to_old.p, s->d_get_scratch.p);
-        HIP_CHECK(hipMemcpyAsync(out, s->d_get_scratch.p, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        return SB_OK;
-    });
+    return guarded([&]() -> int { return get_state_owned(s, out, velocity, nullptr); });
 }
 
 extern "C" {
@@ -83,23 +86,11 @@ const std::vector<int32_t> &local_of_old(sb_solver *s) {
     return s->local_of_old;
 }
 
-// Where a render snapshot of this rank reads the tick-end positions from, made valid on the solver's stream: while the tick's last kernel
-// is held back that is a PEEK into the side array (compact: only the T0 tiles that hold a particle of `wanted_local`; the subset is built
-// once per render set), else the state itself after the tick has been completed. Pending kinematic targets show in a peek.
-const float *render_source(sb_solver *s, bool compact, const std::vector<int32_t> &wanted_local) {
-    if (!can_peek(s)) { flush_deferred(s); return s->d_pos3.p; }
-    if (compact && s->n_peek_tiles < 0) build_peek_subset(s, wanted_local);
-    peek_positions(s, compact);
-    if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p);
-    return s->d_peek.p;
-}
-
+// sb_get_bounds: on what sb_get_positions would return now
 int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]) {
     int rc = set_device(s); if (rc) return rc;
-    const bool peek = can_peek(s);
-    if (peek) { peek_positions(s, false); if (s->kin_pending >= 0) scatter_kinematic(s, s->d_peek.p); }     // (as get_state_owned reads positions)
-    else flush_deferred(s);
-    launch_bounds(s->stream, s->render.bnd, ReadbackBounds::kQuerySlot, peek ? s->d_peek.p : s->d_pos3.p, nullptr, s->n_owned, s->dev_bytes);
+    const float *xyz = tick_end_positions(s);
+    launch_bounds(s->stream, s->render.bnd, ReadbackBounds::kQuerySlot, xyz, nullptr, s->n_owned, s->dev_bytes);
     HIP_CHECK(hipStreamSynchronize(s->stream));
     check_peer_error(s);
     s->render.bnd.read(ReadbackBounds::kQuerySlot, lo, hi);
@@ -145,27 +136,16 @@ int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t co
     }
     if (n_mine == 0) return SB_OK;
     if (s->kin_pending >= 0) flush_deferred(s);       // two moves without a tick between them: the earlier one takes effect first
-    const int q = s->kin_next;
-    s->kin_next = (q + 1) % sb_solver::kKinSlots;
-    if (!s->ev_kin[q]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_kin[q], hipEventDisableTiming));
-    else HIP_CHECK(hipEventSynchronize(s->ev_kin[q]));       // the kernel that read this table (four calls ago) is done
-    if (s->kin_cap[q] < (size_t)n_mine) {
-        if (s->h_kin_idx[q]) { (void)hipHostFree(s->h_kin_idx[q]); s->h_kin_idx[q] = nullptr; }
-        if (s->h_kin_pos[q]) { (void)hipHostFree(s->h_kin_pos[q]); s->h_kin_pos[q] = nullptr; }
-        const size_t cap = std::max<size_t>(256, (size_t)n_mine * 2);
-        // mapped pinned memory: the kernels read the tables in place, through the device-side alias of the allocation
-        HIP_CHECK(hipHostMalloc((void **)&s->h_kin_idx[q], cap * sizeof(int32_t), hipHostMallocMapped));
-        HIP_CHECK(hipHostMalloc((void **)&s->h_kin_pos[q], cap * 3 * sizeof(float), hipHostMallocMapped));
-        HIP_CHECK(hipHostGetDevicePointer((void **)&s->d_kin_idx[q], s->h_kin_idx[q], 0));
-        HIP_CHECK(hipHostGetDevicePointer((void **)&s->d_kin_pos[q], s->h_kin_pos[q], 0));
-        s->kin_cap[q] = cap;
-    }
+    const size_t pos_at = sb_solver::kin_table_pos_at(n_mine);
+    const int q = s->kin_ring.acquire(pos_at + (size_t)n_mine * 3 * sizeof(float));
+    int32_t *h_idx = (int32_t *)s->kin_ring.host(q);
+    float *h_pos = (float *)(s->kin_ring.host(q) + pos_at);
     int32_t w = 0;
     for (int32_t k = 0; k < count; ++k) {
         const int32_t l = lof[(size_t)ids[k]];
         if (l < 0 || l >= s->n_owned) continue;
-        s->h_kin_idx[q][w] = l;
-        for (int c = 0; c < 3; ++c) s->h_kin_pos[q][3 * (size_t)w + c] = pos[3 * (size_t)k + c];
+        h_idx[w] = l;
+        for (int c = 0; c < 3; ++c) h_pos[3 * (size_t)w + c] = pos[3 * (size_t)k + c];
         ++w;
     }
     // PENDING until the next tick starts (the previous tick's held-back last kernel still reads the old positions of these
@@ -191,10 +171,6 @@ int sb_set_kinematic_positions(sb_solver *s, const int32_t *ids, const float *po
     if (count == 0) return SB_OK;
     return guarded([&]() -> int { return set_kinematic(s, ids, pos, count); });
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int sb_get_bounds(sb_solver *s, float lo_xyz[3], float hi_xyz[3]) {
     if (!s || !lo_xyz || !hi_xyz) return fail(SB_ERR_INVALID_ARG, "sb_get_bounds: null argument");

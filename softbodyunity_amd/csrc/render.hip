@@ -47,7 +47,7 @@ void launch_skin(hipStream_t st, const float *src_xyz, const int4 *cage, const f
 }
 
 void ReadbackBounds::prepare(int64_t &acct) {
-    if (box.h) return;
+    if (box.h.p) return;
     d_partials.alloc((size_t)2 * 6 * sbk::kBoundsMaxGroups, acct);
     box.alloc((size_t)8 * (kSnapSlots + 1), acct);
 }
@@ -59,7 +59,7 @@ void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz
     if (groups) hipLaunchKernelGGL(sbk::bounds_partial_kernel, dim3((unsigned)groups), dim3(sbk::kBoundsLanes), 0, st, xyz, rows, (int)count, partials);
     hipLaunchKernelGGL(sbk::bounds_final_kernel, dim3(1), dim3(sbk::kBoundsLanes), 0, st, partials, groups, B.box.d.p + 8 * (size_t)slot);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(B.box.h + 8 * (size_t)slot, B.box.d.p + 8 * (size_t)slot, 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(B.box.h.p + 8 * (size_t)slot, B.box.d.p + 8 * (size_t)slot, 8 * sizeof(float), hipMemcpyDeviceToHost, st));
 }
 
 static_assert(sizeof(sb_ray_hit) == sizeof(uint4), "raycast_final_kernel writes an sb_ray_hit as one 16-byte store");
@@ -69,7 +69,7 @@ void ReadbackRaycast::prepare(int64_t &acct) {
     rays.alloc((size_t)8 * sbk::kRayBatch, acct);
     hits.alloc((size_t)sbk::kRayBatch, acct);
     d_partials.alloc((size_t)sbk::kRayMaxGroups * sbk::kRayBatch, acct);
-    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    stream.create();
 }
 
 // SPEC.md 6c, static part: (dv2, dv1, du1, du2) / det per triangle in f32, zeros where det == 0 or a quotient is not finite. Host code of a
@@ -95,7 +95,7 @@ void RenderTangents::prepare(const std::vector<int32_t> &tri, size_t n_rows, int
         d_k.upload(k, acct);
         dirty = false;
     }
-    if (rows < n_rows || !tan[kSnapSlots - 1].h) {
+    if (rows < n_rows || !tan[kSnapSlots - 1].h.p) {
         for (auto &t : tan) t.alloc(n_rows, acct);
         rows = n_rows;
     }
@@ -160,7 +160,7 @@ const float *end_slot(RenderState &R) {
     const int k = R.head;
     R.last_ended = k;
     R.head = (R.head + 1) % kSnapSlots; --R.pending;
-    return R.slot[k].embedded ? R.emb.pos[k].h : (R.slot[k].compact ? R.cpos[k].h : R.pos[k].h);
+    return R.slot[k].embedded ? R.emb.pos[k].h.p : (R.slot[k].compact ? R.cpos[k].h.p : R.pos[k].h.p);
 }
 
 int set_render_triangles(const char *who, RenderState &R, int32_t n, const int32_t *tri, int32_t m) {
@@ -234,13 +234,13 @@ int set_readback_render_set_only(const char *who, RenderState &R, int32_t on) {
 int readback_get_normals(const char *who, RenderState &R, const float **out) {
     const int k = R.last_ended;
     if (k < 0 || !R.slot[k].has_normals) return fail(SB_ERR_STATE, std::string(who) + ": no finished readback with render triangles set");
-    *out = R.slot[k].embedded ? R.emb.nrm[k].h : R.nrm[k].h;
+    *out = R.slot[k].embedded ? R.emb.nrm[k].h.p : R.nrm[k].h.p;
     return SB_OK;
 }
 
 int readback_get_tangents(const char *who, RenderState &R, const float **out) {
     if (R.last_ended < 0 || !R.tan.snap_has[R.last_ended]) return fail(SB_ERR_STATE, std::string(who) + ": no finished readback with render UVs set");
-    *out = reinterpret_cast<const float *>(R.tan.tan[R.last_ended].h);
+    *out = reinterpret_cast<const float *>(R.tan.tan[R.last_ended].h.p);
     return SB_OK;
 }
 
@@ -285,15 +285,15 @@ int readback_raycast(const char *who, RenderState &R, const float *rays, int32_t
     const int groups = (int)std::min<int64_t>(((int64_t)m + sbk::kRayLanes - 1) / sbk::kRayLanes, sbk::kRayMaxGroups);
     for (int64_t done = 0; done < count; done += sbk::kRayBatch) {
         const int nb = (int)std::min<int64_t>(count - done, sbk::kRayBatch);
-        std::memcpy(Q.rays.h, rays + 8 * done, (size_t)nb * 8 * sizeof(float));
-        HIP_CHECK(hipMemcpyAsync(Q.rays.d.p, Q.rays.h, (size_t)nb * 8 * sizeof(float), hipMemcpyHostToDevice, Q.stream));
+        std::memcpy(Q.rays.h.p, rays + 8 * done, (size_t)nb * 8 * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(Q.rays.d.p, Q.rays.h.p, (size_t)nb * 8 * sizeof(float), hipMemcpyHostToDevice, Q.stream));
         hipLaunchKernelGGL(sbk::raycast_partial_kernel, dim3((unsigned)groups, (unsigned)((nb + sbk::kRayTile - 1) / sbk::kRayTile)), dim3(sbk::kRayLanes), 0, Q.stream, xyz,
                            T.d_tri.p, m, Q.rays.d.p, nb, Q.d_partials.p);
         hipLaunchKernelGGL(sbk::raycast_final_kernel, dim3((unsigned)nb), dim3(sbk::kRayLanes), 0, Q.stream, Q.d_partials.p, groups, Q.hits.d.p);
         HIP_CHECK(hipGetLastError());
         Q.hits.copy_out(Q.stream, (size_t)nb);
         HIP_CHECK(hipStreamSynchronize(Q.stream));
-        std::memcpy(hits_out + done, Q.hits.h, (size_t)nb * sizeof(sb_ray_hit));
+        std::memcpy(hits_out + done, Q.hits.h.p, (size_t)nb * sizeof(sb_ray_hit));
     }
     return SB_OK;
 }
@@ -323,7 +323,7 @@ static void begin_embedded(sb_solver *s, int k) {
         s->n_peek_tiles = -1;       // the peek's tile subset follows the cage particles
     }
     // skinning on the compute stream (ordered after every tick enqueued so far, before the next one) ...
-    const float *src = render_source(s, /*compact=*/true, s->cage_local);
+    const float *src = tick_end_positions(s, /*subset=*/true, s->cage_local);
     launch_skin(s->stream, src, E.d_cage.p, E.d_w.p, E.pos[k].d.p, (int)E.m);
     HIP_CHECK(hipEventRecord(s->ev_snap[k], s->stream));
     // ... normals (SPEC.md 6a on the skinned array) and D2H on the copy stream
@@ -349,23 +349,24 @@ int sb_readback_begin(sb_solver *s) {
     return guarded([&]() -> int {
         int rc = set_device(s); if (rc) return rc;
         RenderState &R = s->render;
-        if (!R.copy_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&R.copy_stream, hipStreamNonBlocking));
+        if (!R.ev_copied[kSnapSlots - 1]) {       // first use, keyed on what it creates last (create() is idempotent)
+            R.copy_stream.create();
             for (int k = 0; k < kSnapSlots; ++k) {
-                HIP_CHECK(hipEventCreateWithFlags(&s->ev_snap[k], hipEventDisableTiming));
-                HIP_CHECK(hipEventCreateWithFlags(&R.ev_copied[k], hipEventDisableTiming));
+                s->ev_snap[k].create(hipEventDisableTiming);
+                R.ev_copied[k].create(hipEventDisableTiming);
             }
         }
         const int k = R.next_slot();
         if (R.emb.m > 0) { begin_embedded(s, k); return SB_OK; }       // (no particle snapshot: its n-sized buffers are not even allocated)
         const size_t n3 = (size_t)s->n * 3;
-        if (!R.pos[kSnapSlots - 1].h) {
+        if (!R.pos[kSnapSlots - 1].h.p) {      // first use: a slot counts as made once its pinned side is there, which comes last
             if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
             for (int q = 0; q < kSnapSlots; ++q) {
-                if (R.pos[q].h) continue;
-                R.pos[q].alloc(n3, s->dev_bytes);
+                if (R.pos[q].h.p) continue;
+                R.pos[q].d.alloc(n3, s->dev_bytes);
                 HIP_CHECK(hipMemset(R.pos[q].d.p, 0, n3 * sizeof(float)));
-                std::memset(R.pos[q].h, 0, n3 * sizeof(float));
+                R.pos[q].pin();
+                std::memset(R.pos[q].h.p, 0, n3 * sizeof(float));
             }
         }
         // snapshot on the compute stream (ordered after every tick enqueued so far, before the next one) ...
@@ -383,14 +384,14 @@ int sb_readback_begin(sb_solver *s) {
             R.d_set.upload(R.set, s->dev_bytes);
             s->d_render_local.upload(s->render_local, s->dev_bytes);
             for (int q = 0; q < kSnapSlots; ++q) {
-                if (single && !R.nrm[q].h) R.nrm[q].alloc(n3, s->dev_bytes);
+                if (single && !R.nrm[q].h.p) R.nrm[q].alloc(n3, s->dev_bytes);
                 R.cpos[q].alloc(R.set.size() * 3, s->dev_bytes);
             }
             R.dirty = false;
             s->n_peek_tiles = -1;
         }
         // the tick's last kernel is deferred: snapshot a peek and leave it deferred
-        const float *src = render_source(s, compact, s->render_local);
+        const float *src = tick_end_positions(s, compact, s->render_local);
         const int cnt = (int)R.set.size();
         // compact: only the render set leaves the device. A single rank snapshots just those particles into the caller-numbered array (the
         // normals kernel gathers neighbours by caller id and emits the compact arrays); a partitioned rank has no normals: straight into the compact array

@@ -1,6 +1,6 @@
 // render.hpp — the render readback's state and stage, shared by a solver (render.hip) and by a group's render device (group.hip): snapshot
 // slots, device buffers with their pinned twins, incident-triangle lists, the embedding, tangents, bounds. Included by solver_internal.hpp
-// (after DevBuf); plain structs and free functions, the owner passes what differs (a count, a pointer, a stream).
+// (after device_handles.hpp: every buffer, stream and event here gives itself back, with the owner's device current); plain structs and free functions, the owner passes what differs (a count, a pointer, a stream).
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 #pragma once
@@ -12,26 +12,6 @@ namespace sbi {
 // three slots, at most two pending: the slot a readback_end handed out last is never the next one to be filled, so its pointer stays
 // valid until the SECOND readback_begin after it (softbody.h, softbody_group.h)
 constexpr int kSnapSlots = 3;
-
-// A device buffer and its pinned host twin of the same size (at least one element), for results that leave by an asynchronous copy.
-template <class T>
-struct Mirror {
-    DevBuf<T> d;
-    T *h = nullptr;
-    void pin() {                           // the host side alone, sized like the device side
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-        HIP_CHECK(hipHostMalloc((void **)&h, std::max<size_t>(d.count, 1) * sizeof(T), hipHostMallocDefault));
-    }
-    void alloc(size_t count, int64_t &acct) { d.alloc(count, acct); pin(); }
-    void copy_out(hipStream_t st, size_t count) { if (count) HIP_CHECK(hipMemcpyAsync(h, d.p, count * sizeof(T), hipMemcpyDeviceToHost, st)); }
-    void release() {
-        d.free();
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-    }
-    ~Mirror() { release(); }
-};
 
 // Render tangents (sb_set_render_uvs, SPEC.md 6c): the UVs of the render mode in force, the per-triangle coefficient table made from
 // them, and per snapshot slot the tangents on the device and in pinned memory.
@@ -67,23 +47,17 @@ struct ReadbackBounds {
     Mirror<float> box;                     // 8 floats per slot
     bool snap_has[kSnapSlots] = {false, false, false};
     void prepare(int64_t &acct);           // buffers, at first use
-    void read(int slot, float lo[3], float hi[3]) const { for (int c = 0; c < 3; ++c) { lo[c] = box.h[8 * slot + c]; hi[c] = box.h[8 * slot + 4 + c]; } }
-    void release() { d_partials.free(); box.release(); }
+    void read(int slot, float lo[3], float hi[3]) const { for (int c = 0; c < 3; ++c) { lo[c] = box.h.p[8 * slot + c]; hi[c] = box.h.p[8 * slot + 4 + c]; } }
 };
 
 // Ray casts (sb_readback_raycast, SPEC.md 6e): a stream of its own -- a cast waits for no pending snapshot's copy -- and, from the first cast
 // on, the buffers of one batch of rays: the rays and the hits with their pinned twins, the workgroups' partials. Larger counts walk in batches.
 struct ReadbackRaycast {
-    hipStream_t stream = nullptr;
+    Stream stream;
     Mirror<float> rays;                    // 8 floats per ray of a batch (the pinned side is the staging of the upload)
     Mirror<uint4> hits;                    // one sb_ray_hit per ray of a batch
     DevBuf<uint4> d_partials;              // (key, u, v) per (ray, workgroup)
-    void prepare(int64_t &acct);           // stream and buffers, at first use
-    void release() {
-        rays.release(); hits.release(); d_partials.free();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
+    void prepare(int64_t &acct);           // buffers and stream, at first use
 };
 
 // Triangles and the incident-triangle lists per vertex (triangle ids ascending: what the normals kernels walk), on the device.
@@ -91,7 +65,7 @@ struct RenderTopology {
     DevBuf<int32_t> d_tri, d_adj_off, d_adj_tri;
     // -> the lists' offsets [n_vertices + 1]: vertex v is used by a triangle where off[v + 1] > off[v]
     std::vector<int32_t> upload(const std::vector<int32_t> &tri, int32_t n_vertices, int64_t &acct);
-    void release() { d_tri.free(); d_adj_off.free(); d_adj_tri.free(); }
+    void release() { d_tri.free(); d_adj_off.free(); d_adj_tri.free(); }      // (RenderEmbedding::release)
 };
 
 // Embedded render vertices (set_render_embedding, SPEC.md 6b): while m > 0 a readback brings the skinned visual mesh instead of the
@@ -115,8 +89,8 @@ struct RenderEmbedding {
 
 // Everything a solver and a group's render device both keep for the render readback.
 struct RenderState {
-    hipStream_t copy_stream = nullptr;     // normals, tangents, bounds and every copy to the host run here, in order (the bounds partials rely on it)
-    hipEvent_t ev_copied[kSnapSlots] = {nullptr, nullptr, nullptr};
+    Stream copy_stream;                    // normals, tangents, bounds and every copy to the host run here, in order (the bounds partials rely on it)
+    Event ev_copied[kSnapSlots];
     int head = 0, pending = 0;             // ring: slots head .. head + pending - 1 (mod kSnapSlots) are in flight
     int last_ended = -1;
     struct Slot { bool compact = false, has_normals = false, has_render_set = false, embedded = false; } slot[kSnapSlots];
@@ -136,11 +110,6 @@ struct RenderState {
     ReadbackBounds bnd;                    // of the delivered array, and of the synchronous query
     ReadbackRaycast ray;                   // casts against the snapshot ended last
     void forget_normals() { for (Slot &q : slot) q.has_normals = q.has_render_set = false; }
-    void release() {                       // every buffer, with the copy stream idle (the owner's destructor)
-        topo.release(); d_set.free();
-        for (int k = 0; k < kSnapSlots; ++k) { pos[k].release(); nrm[k].release(); cpos[k].release(); }
-        emb.release(); tan.release(); bnd.release(); ray.release();
-    }
 };
 
 // ---- render.hip: the kernels' launch helpers (dst of a snapshot may live on another device) ----------------------------------------------

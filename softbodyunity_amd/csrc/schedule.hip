@@ -41,8 +41,8 @@ void peer_link(sb_solver *s) {
         sbk::PeerSlot &P = PS.slots[(size_t)slot];
         const size_t base = PS.slot_base(slot, W);
         const size_t fl = slot == 1 ? 6 : 3;
-        P.local = PS.local + (size_t)slot * 8;
-        P.error = PS.h_error;         // (pinned host memory is device-accessible at the same address)
+        P.local = PS.local.p + (size_t)slot * 8;
+        P.error = PS.h_error.p;       // (pinned host memory is device-accessible at the same address)
         for (size_t k = 0; k < D.peers.size(); ++k) {
             const int r = s->loopback ? me : D.peers[k];
             int cs = D.send_off[k + 1] - D.send_off[k], cr = D.recv_off[k + 1] - D.recv_off[k];
@@ -176,15 +176,16 @@ void halo_exchange_post(sb_solver *s, int slot, hipStream_t st) {
 // Exchange timing (sb_debug_exchange_timing): three events per exchange on the stream it runs on -- start, after the pack (or push)
 // kernel, end -- resolved when the host reads the sums.
 void ExchangeTimer::mark(hipStream_t st, bool join) {
-    hipEvent_t e;
-    if (free_list.empty()) HIP_CHECK(hipEventCreate(&e)); else { e = free_list.back(); free_list.pop_back(); }
+    Event e;
+    if (free_list.empty()) e.create(); else { e = std::move(free_list.back()); free_list.pop_back(); }
     HIP_CHECK(hipEventRecord(e, st));
-    (join ? join_pending : pending).push_back(e);
+    (join ? join_pending : pending).push_back(std::move(e));
 }
-ExchangeTimer::~ExchangeTimer() {
-    for (auto e : pending) (void)hipEventDestroy(e);
-    for (auto e : join_pending) (void)hipEventDestroy(e);
-    for (auto e : free_list) (void)hipEventDestroy(e);
+void ExchangeTimer::recycle() {
+    for (auto *v : {&pending, &join_pending}) {
+        free_list.insert(free_list.end(), std::make_move_iterator(v->begin()), std::make_move_iterator(v->end()));
+        v->clear();
+    }
 }
 
 void halo_exchange(sb_solver *s, int slot, hipStream_t st) {
@@ -273,17 +274,16 @@ void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = 
 }
 
 struct LaunchTimer {            // optional HIP-event pair around every launch of one tick (sb_step_profiled)
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     std::vector<int> slot;      // see sb_step_profiled in softbody.h
     hipStream_t stream;
     void begin(int which) {
-        hipEvent_t a, b;
-        HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        ev.push_back(a); ev.push_back(b); slot.push_back(which);
+        Event a, b;
+        a.create(); b.create();
         HIP_CHECK(hipEventRecord(a, stream));
+        ev.push_back(std::move(a)); ev.push_back(std::move(b)); slot.push_back(which);
     }
     void end() { HIP_CHECK(hipEventRecord(ev.back(), stream)); }
-    ~LaunchTimer() { for (auto e : ev) (void)hipEventDestroy(e); }
 };
 
 // Launch the tile kernel K_it of a tick of `substeps` substeps (no halo).
@@ -414,19 +414,25 @@ void enqueue_substeps(sb_solver *s, int substeps, LaunchTimer *lt = nullptr, boo
     HIP_CHECK(hipGetLastError());
 }
 
-// Launch the deferred last kernel of the previous tick (uses the tick parameters still on the device).
+// The two arrays of the pending targets' table (set_kinematic wrote it), as the kernels see them.
+struct KinTable { const int32_t *idx; const float *pos; int count; };
+static KinTable pending_kinematic(const sb_solver *s) {
+    const char *d = s->kin_ring.device(s->kin_pending);
+    return KinTable{(const int32_t *)d, (const float *)(d + sb_solver::kin_table_pos_at(s->kin_pending_count)), s->kin_pending_count};
+}
 // Pending kinematic targets onto `dst` (the positions, or the peek's side array): scatter kernel over the pinned host table.
 void scatter_kinematic(sb_solver *s, float *dst) {
-    const int q = s->kin_pending, count = s->kin_pending_count;
-    hipLaunchKernelGGL(sbk::kinematic_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s->stream, dst, s->d_kin_idx[q], s->d_kin_pos[q], count);
+    const KinTable K = pending_kinematic(s);
+    hipLaunchKernelGGL(sbk::kinematic_scatter_kernel, dim3((unsigned)((K.count + 255) / 256)), dim3(256), 0, s->stream, dst, K.idx, K.pos, K.count);
     HIP_CHECK(hipGetLastError());
 }
 // The table of the pending targets has been handed to its last reader: it may be reused once that kernel is done.
 void retire_kinematic(sb_solver *s) {
-    HIP_CHECK(hipEventRecord(s->ev_kin[s->kin_pending], s->stream));
+    s->kin_ring.retire(s->kin_pending, s->stream);
     s->kin_pending = -1; s->kin_pending_count = 0;
 }
 
+// Launch the deferred last kernel of the previous tick (uses the tick parameters still on the device); pending targets then take effect.
 void flush_deferred(sb_solver *s) {
     if (s->deferred) {
         const int S = s->deferred_substeps;
@@ -444,18 +450,18 @@ void flush_deferred(sb_solver *s) {
 // Everything a fused first kernel needs to apply the pending targets itself: the particle -> slot map (built once), the slot
 // array (NaN = no target), and this tick's targets written into their slots on the solver's stream.
 void stage_kinematic_for_fusion(sb_solver *s) {
-    if (!s->d_kin_map.p) {
+    if (!s->d_kin_map.p) {       // first use, keyed on the map: uploaded last, behind the slots it points into
         const sbp::LocalPlan &L = s->plan->local;
         std::vector<int32_t> map((size_t)s->n_local, -1);
         int32_t n_pinned = 0;
         for (int64_t l = 0; l < s->n_local; ++l) if (s->invm[(size_t)L.local_to_old[(size_t)l]] == 0.0f) map[(size_t)l] = n_pinned++;
-        s->d_kin_map.upload(map, s->dev_bytes);
         std::vector<float> nan((size_t)std::max(n_pinned, 1) * 3, std::numeric_limits<float>::quiet_NaN());
         s->d_kin_target.upload(nan, s->dev_bytes);
+        s->d_kin_map.upload(map, s->dev_bytes);
     }
-    const int q = s->kin_pending, count = s->kin_pending_count;
-    hipLaunchKernelGGL(sbk::kinematic_fill_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s->stream, s->d_kin_map.p, s->d_kin_target.p,
-                       s->d_kin_idx[q], s->d_kin_pos[q], count);
+    const KinTable K = pending_kinematic(s);
+    hipLaunchKernelGGL(sbk::kinematic_fill_kernel, dim3((unsigned)((K.count + 255) / 256)), dim3(256), 0, s->stream, s->d_kin_map.p, s->d_kin_target.p,
+                       K.idx, K.pos, K.count);
     HIP_CHECK(hipGetLastError());
     retire_kinematic(s);
 }
@@ -521,20 +527,12 @@ void upload_tick_params(sb_solver *s, float dt, int substeps) {
 
 // Peer transport: a wait that gave up (a neighbour never delivered / never acknowledged) must not pass silently.
 void check_peer_error(sb_solver *s) {
-    if (!s->peer.enabled || !s->peer.h_error) return;
-    const uint32_t flag = *reinterpret_cast<volatile uint32_t *>(s->peer.h_error);     // a host load: cheap enough for every sb_step
+    if (!s->peer.enabled || !s->peer.h_error.p) return;
+    const uint32_t flag = *reinterpret_cast<volatile uint32_t *>(s->peer.h_error.p);     // a host load: cheap enough for every sb_step
     if (flag) throw HipError(SB_ERR_RCCL, "peer transport: a halo wait gave up (a neighbour never delivered or never acknowledged)");
 }
 
-}  // namespace sbi
-
-using namespace sbi;
-
-extern "C" {
-
-}  // extern "C"  (the pieces of a tick are shared with group.hip)
-
-namespace sbi {
+// (the pieces of a tick are shared with group.hip)
 
 // What the next tick will look like, decided from the solver's state alone -- the ranks of a partitioned solver are in the same state,
 // so they all decide the same: `fuse` = its first kernel also finishes the previous tick (lazy tick boundary), `defer_last` = its own
@@ -577,7 +575,7 @@ void calibrate_before_tick(sb_solver *s) {
         s->overlap_halo = (k & 1) != 0;
         if (k >= kCalibWarmTicks) {
             const int q = 2 * (k - kCalibWarmTicks);
-            if (!C.ev[q]) { HIP_CHECK(hipEventCreate(&C.ev[q])); HIP_CHECK(hipEventCreate(&C.ev[q + 1])); }
+            C.ev[q].create(); C.ev[q + 1].create();
             HIP_CHECK(hipEventRecord(C.ev[q], s->stream));
         }
         return;
@@ -616,6 +614,8 @@ void calibrate_after_tick(sb_solver *s) {
 }
 
 }  // namespace sbi
+
+using namespace sbi;
 
 extern "C" {
 
@@ -679,9 +679,7 @@ int sb_debug_exchange_timing(sb_solver *s, int32_t enabled) {
         if (!enabled && s->xtimer.enabled) {       // drop what was not read
             HIP_CHECK(hipStreamSynchronize(s->stream));
             if (s->comm_stream) HIP_CHECK(hipStreamSynchronize(s->comm_stream));
-            s->xtimer.free_list.insert(s->xtimer.free_list.end(), s->xtimer.pending.begin(), s->xtimer.pending.end());
-            s->xtimer.free_list.insert(s->xtimer.free_list.end(), s->xtimer.join_pending.begin(), s->xtimer.join_pending.end());
-            s->xtimer.pending.clear(); s->xtimer.join_pending.clear();
+            s->xtimer.recycle();
         }
         s->xtimer.enabled = enabled != 0;
         return SB_OK;
@@ -708,9 +706,7 @@ int sb_debug_exchange_timing_read(sb_solver *s, sb_exchange_timing *out) {
             HIP_CHECK(hipEventElapsedTime(&w, X.join_pending[k], X.join_pending[k + 1]));
             out->exposed_wait_ms += w;
         }
-        X.free_list.insert(X.free_list.end(), X.pending.begin(), X.pending.end());
-        X.free_list.insert(X.free_list.end(), X.join_pending.begin(), X.join_pending.end());
-        X.pending.clear(); X.join_pending.clear();
+        X.recycle();
         return SB_OK;
     });
 }

@@ -1,9 +1,9 @@
-// solver_internal.hpp — what the translation units of libsoftbody_mi355x.so share: error plumbing, the run-time RCCL binding, device
-// buffers, the solver object. Nothing declared here is exported (exports.map keeps the dynamic symbol table to sb_*).
+// solver_internal.hpp — what the translation units of libsoftbody_mi355x.so share: error plumbing, the run-time RCCL binding, the
+// solver object (what owns its device resources: device_handles.hpp). Nothing declared here is exported (exports.map keeps the dynamic symbol table to sb_*).
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
-// Units: binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
-// tick), readback.hip (state reads / writes, kinematic targets), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
+// Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
+// tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
@@ -86,32 +86,10 @@ RcclApi &rccl(bool required = true);
 int hip_runtime_version();
 bool capture_overlap_ok();      // see binding.hip
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    T *base = nullptr;           // what hipMalloc returned (p = base + lead: placement experiments, sb_tuning.prev_offset_bytes)
-    size_t count = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;                 // owns device memory
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), base(o.base), count(o.count) { o.p = o.base = nullptr; o.count = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { free(); p = o.p; base = o.base; count = o.count; o.p = o.base = nullptr; o.count = 0; } return *this; }
-    void alloc(size_t n, int64_t &acct, size_t lead_elems = 0) {
-        free();
-        count = n;
-        if (n) { HIP_CHECK(hipMalloc((void **)&base, (n + lead_elems) * sizeof(T))); p = base + lead_elems; acct += (int64_t)((n + lead_elems) * sizeof(T)); }
-    }
-    void upload(const std::vector<T> &h, int64_t &acct) {
-        alloc(h.size(), acct);
-        if (!h.empty()) HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    }
-    void free() { if (base) { (void)hipFree(base); } base = nullptr; p = nullptr; count = 0; }
-    ~DevBuf() { free(); }
-};
-
 }  // namespace sbi
 
-#include "render.hpp"      // the render readback's state (needs DevBuf)
+#include "device_handles.hpp"      // Event, Stream, DevBuf, HostBuf, Mirror, TableRing (need HIP_CHECK)
+#include "render.hpp"      // the render readback's state (needs them)
 
 namespace sbi {
 
@@ -157,9 +135,9 @@ struct TickShape { int substeps; bool fuse, defer_last, kin; };
 // sb_debug_exchange_timing: three events per exchange (start, after the pack / push kernel, end) on the stream it runs on
 struct ExchangeTimer {
     bool enabled = false;
-    std::vector<hipEvent_t> pending, join_pending, free_list;      // join_pending: pairs around the compute stream's wait for an overlapped exchange
+    std::vector<Event> pending, join_pending, free_list;      // join_pending: pairs around the compute stream's wait for an overlapped exchange
     void mark(hipStream_t st, bool join = false);
-    ~ExchangeTimer();
+    void recycle();         // everything pending -> free_list
 };
 
 }  // namespace sbi
@@ -176,14 +154,14 @@ struct sb_plan {
 struct sb_solver {
     sb_desc desc;
     bool finalized = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    sbi::Stream stream;
+    sbi::Event ev0, ev1;
     ncclComm_t comm = nullptr;
     bool loopback = false;           // SB_DEBUG_LOOPBACK: every peer is this rank itself (1-GPU pipeline test)
     int schedule = SB_SCHEDULE_SERIAL_EAGER;   // world > 1: what desc.halo_schedule resolved to (sb_finalize)
     uint64_t plan_hash = 0;          // hash of the published orders, ownership and plan options (equal on every rank)
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_boundary = nullptr, ev_halo = nullptr;
+    sbi::Stream comm_stream;
+    sbi::Event ev_boundary, ev_halo;
     bool overlap_halo = false;       // T0 boundary tiles first, ghost exchange on comm_stream beside the interior
     // authoring copies
     int32_t n = 0;
@@ -248,7 +226,7 @@ struct sb_solver {
     struct AutoSchedule {
         int state = 0;                       // 0 off, 1 calibrating, 2 decided
         int tick = 0;                        // sb_step calls so far
-        hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // start / end of the four timed ticks
+        sbi::Event ev[8];                    // start / end of the four timed ticks
         int n[2] = {0, 0};                   // ticks timed per schedule
         double decided_ms[2] = {0, 0};       // per tick, slowest rank: [0] serialised, [1] overlapped
     } calib;
@@ -265,48 +243,41 @@ struct sb_solver {
         std::vector<uint8_t> opened;            // remote[r] was mapped with hipIpcOpenMemHandle
         std::vector<std::vector<uint32_t>> my_off;   // [slot][rank]: first word (from the mailbox start) of rank's segment in MY mailbox
         std::vector<sbk::PeerSlot> slots;
-        uint32_t *local = nullptr;              // 8 ordinary (cached) words per slot: epoch, workgroup counters, go words
-        uint32_t *h_error = nullptr;            // pinned host word the kernels set when a wait gives up: the host reads it without a copy
+        DevBuf<uint32_t> local;                 // 8 ordinary (cached) words per slot: epoch, workgroup counters, go words
+        sbi::HostBuf<uint32_t> h_error;         // pinned host word the kernels set when a wait gives up: the host reads it without a copy
         size_t slot_base(int slot, int world) const { return sbt::mailbox_slot_base(slot, world); }
+        // ORDER: the mappings of the neighbours' mailboxes are closed before this rank's own mailbox is freed (tables.hip alloc_mailbox made it)
+        ~PeerState() {
+            for (size_t r = 0; r < remote.size(); ++r) if (opened[r] && remote[r]) (void)hipIpcCloseMemHandle(remote[r]);
+            if (mailbox) (void)hipFree(mailbox);
+        }
     } peer;
     // asynchronous render readback (sb_readback_begin / sb_readback_end; render.hpp): what a group's render device keeps too ...
     sbi::RenderState render;
     // ... and what is this rank's own: the snapshot runs on the compute stream, in device numbering
-    hipEvent_t ev_snap[sbi::kSnapSlots] = {nullptr, nullptr, nullptr};
+    sbi::Event ev_snap[sbi::kSnapSlots];
     DevBuf<int32_t> d_local_to_old;
     DevBuf<float> d_get_scratch;           // caller-numbered staging of the blocking sb_get_* calls (world == 1)
     DevBuf<int32_t> d_render_local;
     std::vector<int32_t> render_local;     // device numbering of render.set's particles
     std::vector<int32_t> cage_local;       // the distinct cage particles of render.emb, device numbering: what a peek has to cover
-    // kinematic targets (sb_set_kinematic_positions): a ring of pinned host tables the scatter kernel reads directly; a table is reused
-    // only after the kernel that read it has finished (its event)
-    static constexpr int kKinSlots = 4;
-    int32_t *h_kin_idx[kKinSlots] = {nullptr, nullptr, nullptr, nullptr};
-    float *h_kin_pos[kKinSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t *d_kin_idx[kKinSlots] = {nullptr, nullptr, nullptr, nullptr};      // device-side aliases of the mapped tables
-    float *d_kin_pos[kKinSlots] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<uint32_t> kin_seen; uint32_t kin_stamp = 0;                    // duplicate-id check of sb_set_kinematic_positions
+    // kinematic targets (sb_set_kinematic_positions): a ring of mapped pinned tables the scatter / fill kernels read in place, one table per
+    // call: [int32 device particle x count][pad to 16 bytes][float xyz x count] (kin_table_pos_at)
+    sbi::TableRing<4> kin_ring;
+    std::vector<uint32_t> kin_seen; uint32_t kin_stamp = 0;     // duplicate-id check of sb_set_kinematic_positions
     std::vector<int32_t> local_of_old;     // the rank's numbering -> device numbering (-1: not held), built at first use (readback.hip)
-    size_t kin_cap[kKinSlots] = {0, 0, 0, 0};
-    hipEvent_t ev_kin[kKinSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int kin_next = 0;
     // Targets are PENDING until the next tick starts: if that tick's first kernel also finishes the tick before (lazy tick boundary),
     // they travel into it (tile_kernel KIND 5 applies them between the old tick's velocity and the new tick's integrate) and the
     // fusion is kept; any other way across the boundary (state read or written, parameters changed, first tick) completes the old
     // tick and scatters them onto the positions (materialise_kinematic).
     int kin_pending = -1, kin_pending_count = 0;      // ring slot that holds them, or -1
+    static size_t kin_table_pos_at(int count) { return ((size_t)count * sizeof(int32_t) + 15) / 16 * 16; }      // where the targets start in a table of `count`
     DevBuf<int32_t> d_kin_map;             // per local particle: slot of a pinned particle, -1 for a free one (built at the first use)
     DevBuf<float> d_kin_target;            // 3 floats per pinned particle: pending target or NaN
     int64_t n_kin_fused = 0;               // ticks whose fused first kernel carried targets
     bool kin_fuse = true;                  // !SB_TUNE_NO_KIN_FUSE (A/B: pending targets always complete the previous tick first)
-    // impulses (sb_apply_impulses, impulse.hip): the sparse kernel's tables travel like the kinematic targets -- a ring of mapped pinned
-    // buffers, each reused only after the kernel that read it has finished (its event); allocated at the first call
-    static constexpr int kImpSlots = 4;
-    void *h_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};
-    void *d_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};         // device-side aliases of the mapped tables
-    size_t imp_cap[kImpSlots] = {0, 0, 0, 0};                              // bytes
-    hipEvent_t ev_imp[kImpSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int imp_next = 0;
+    // impulses (sb_apply_impulses, impulse.hip): the sparse kernels' tables travel like the kinematic targets, one table per call
+    sbi::TableRing<4> imp_ring;
     // Peek (world == 1): a position read while the tick's last kernel is deferred runs tile_kernel<4> -- the same rounds + collide on
     // the same inputs, written to d_peek instead of the state -- so the deferred kernel can still be fused with the next tick's first
     // one. A render-set-only readback peeks only at the T0 tiles that hold a render particle (peek_tiles: copies of their descriptors).
@@ -322,43 +293,19 @@ struct sb_solver {
     int64_t n_peeks = 0;                   // launches so far (sb_stats.readback_peeks)
     int64_t n_fused = 0;                   // ticks that started with the fused kernel (sb_stats.ticks_fused)
 
+    // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
+    // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
     ~sb_solver() {
-        // Teardown order: everything the device may still be running for this solver first (compute, exchange and copy
-        // streams), then the graph executables (captured RCCL launches hold references into the communicator), then the
-        // communicator, then the streams and events.
+        // 1. everything the device may still be running for this solver: compute, exchange and render copy stream
         if (stream) (void)hipStreamSynchronize(stream);
         if (comm_stream) (void)hipStreamSynchronize(comm_stream);
         if (render.copy_stream) (void)hipStreamSynchronize(render.copy_stream);
+        // 2. the graph executables before the communicator: captured RCCL launches hold references into it
         for (auto &g : graphs) (void)hipGraphExecDestroy(g.second.exec);
         graphs.clear();
+        // 3. the communicator before the streams it was used on (members: they go after this body)
         if (comm) (void)sbi::rccl(false).CommDestroy(comm);
-        for (size_t r = 0; r < peer.remote.size(); ++r) if (peer.opened[r] && peer.remote[r]) (void)hipIpcCloseMemHandle(peer.remote[r]);
-        if (peer.mailbox) (void)hipFree(peer.mailbox);
-        if (peer.local) (void)hipFree(peer.local);
-        if (peer.h_error) (void)hipHostFree(peer.h_error);
-        for (hipEvent_t e : calib.ev) if (e) (void)hipEventDestroy(e);
-        if (ev_boundary) (void)hipEventDestroy(ev_boundary);
-        if (ev_halo) (void)hipEventDestroy(ev_halo);
-        if (comm_stream) (void)hipStreamDestroy(comm_stream);
-        gcolours.clear(); halos.clear();
-        for (int k = 0; k < sbi::kSnapSlots; ++k) {
-            if (ev_snap[k]) (void)hipEventDestroy(ev_snap[k]);
-            if (render.ev_copied[k]) (void)hipEventDestroy(render.ev_copied[k]);
-        }
-        render.release();
-        if (render.copy_stream) (void)hipStreamDestroy(render.copy_stream);
-        for (int k = 0; k < kKinSlots; ++k) {
-            if (h_kin_idx[k]) (void)hipHostFree(h_kin_idx[k]);
-            if (h_kin_pos[k]) (void)hipHostFree(h_kin_pos[k]);
-            if (ev_kin[k]) (void)hipEventDestroy(ev_kin[k]);
-        }
-        for (int k = 0; k < kImpSlots; ++k) {
-            if (h_imp[k]) (void)hipHostFree(h_imp[k]);
-            if (ev_imp[k]) (void)hipEventDestroy(ev_imp[k]);
-        }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
+        // (4. IPC mappings before the mailbox: ~PeerState)
     }
 };
 
@@ -400,7 +347,8 @@ const std::vector<int32_t> &local_of_old(sb_solver *s);
 int get_state_owned(sb_solver *s, float *out, bool velocity, const int32_t *id_map);
 int set_state_from(sb_solver *s, const float *pos, const float *vel, const int32_t *id_map);
 int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t count);
-const float *render_source(sb_solver *s, bool compact, const std::vector<int32_t> &wanted_local);
+// where the tick-end positions are, made valid on the solver's stream (the caller synchronises): a peek while the last kernel is held back
+const float *tick_end_positions(sb_solver *s, bool subset = false, const std::vector<int32_t> &wanted_local = {});
 // sb_get_bounds: the box of the particles this rank owns, on what sb_get_positions would return now (peeks where that peeks)
 int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]);
 

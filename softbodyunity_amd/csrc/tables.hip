@@ -89,10 +89,11 @@ static void alloc_mailbox(sb_solver *s, sbt::HostMailbox &M) {
     s->dev_bytes += (int64_t)PS.bytes;
     HIP_CHECK(hipMemset(PS.mailbox, 0, PS.bytes));
     HIP_CHECK(hipMemcpy(PS.mailbox, M.header.data(), M.header.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc((void **)&PS.local, (size_t)PS.n_slots * 8 * sizeof(uint32_t)));
-    HIP_CHECK(hipMemset(PS.local, 0, (size_t)PS.n_slots * 8 * sizeof(uint32_t)));
-    HIP_CHECK(hipHostMalloc((void **)&PS.h_error, sizeof(uint32_t), hipHostMallocMapped));
-    *PS.h_error = 0;
+    int64_t unaccounted = 0;       // (sb_stats.device_bytes counts the mailbox, not these 32 bytes per slot)
+    PS.local.alloc((size_t)PS.n_slots * 8, unaccounted);
+    HIP_CHECK(hipMemset(PS.local.p, 0, (size_t)PS.n_slots * 8 * sizeof(uint32_t)));
+    PS.h_error.alloc(1, /*mapped=*/true);
+    *PS.h_error.p = 0;
     PS.remote.assign((size_t)W, nullptr);
     PS.opened.assign((size_t)W, 0);
     PS.remote[(size_t)s->plan->local.rank] = PS.mailbox;

@@ -91,6 +91,44 @@ def test_only_pinned_particles_are_kinematic_and_nothing_changes_on_error():
         sb.OnDestroy()
 
 
+def test_target_tables_regrow_while_the_ring_wraps(oracle_mod):
+    # Lists of changing length, well past a table's 256-entry floor (the earlier wrap test never leaves it): nine calls wrap the ring of
+    # four tables twice -- the slots see 100, 700, 50 / 300, 10 / 650, 400 / 120, 700 targets, so tables are regrown on a later use, and
+    # small lists land in tables grown for large ones -- and a step after every call lets the fused first kernel (tile_kernel KIND 5)
+    # read each table in place. The second phase goes round once more without a tick in between.
+    mesh = jelly_cube(10)
+    pins = np.arange(700, dtype=np.int32)
+    mesh.inv_mass[pins] = 0.0
+    rest = mesh.pos.copy()
+    sb = Softbody(mesh, substeps=4).Start()
+    try:
+        o = make_oracle(oracle_mod, mesh, sb.plan())
+
+        def move(count, k):
+            ids = pins[:count]
+            target = rest[ids] + np.array([0.01 * k, -0.005 * k, 0.002 * k * k], np.float32)
+            sb.set_kinematic_positions(ids, target)
+            o.set_kinematic_positions(ids, target)
+
+        fused_before = sb.stats()["ticks_fused_kinematic"]
+        for k, count in enumerate([100, 300, 650, 120, 700, 10, 400, 700, 50]):
+            move(count, k + 1)
+            sb.step()
+            o.step(0.02, 4)
+        x, v = sb.get_positions(), sb.get_velocities()
+        assert np.array_equal(_bits(x), _bits(o.x)) and np.array_equal(_bits(v), _bits(o.v))
+        assert sb.stats()["ticks_fused_kinematic"] > fused_before          # (not by never fusing)
+        # three calls without a step between them: each later call completes the tick and scatters the earlier one
+        for k, count in enumerate([300, 650, 700]):
+            move(count, 20 + k)
+        sb.step()
+        o.step(0.02, 4)
+        x = sb.get_positions()
+        assert np.array_equal(_bits(x[pins]), _bits(o.x[pins]))
+    finally:
+        sb.OnDestroy()
+
+
 def test_a_rank_of_a_partitioned_solver_moves_the_pins_it_owns(oracle_mod):
     # every rank is handed the whole list; it applies the entries it owns (the ghost copies on its neighbours arrive with the next
     # exchange) -- here 8 ranks of one mesh on the one GPU, the host as the wire (tests/hosted.py), against the oracle
