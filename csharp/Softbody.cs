@@ -3,6 +3,7 @@
 // Start()       -> sb_group_create + sb_group_set_particles/sb_group_set_*_constraints + sb_group_finalize   (plan, partition, upload)
 // FixedUpdate() -> sb_group_step(Time.fixedDeltaTime, substeps) + sb_group_get_positions                     (one tick, SPEC.md §2)
 //                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
+//                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
 // OnDestroy()   -> sb_group_destroy
 //
 // A Unity player is ONE process: the component talks to the plugin through include/softbody_group.h, where `deviceCount` GPUs sit
@@ -57,6 +58,8 @@ namespace SoftbodyMI355X
         [SerializeField] bool renderSetOnly = false;
         [Tooltip("With asyncReadback on a tet cage (volumeIJKL): a separate, finer visual mesh. It is bound to the cage at Start (SoftbodyMeshBuilder.EmbedVertices) and skinned on the GPU every tick (SPEC.md 6b); the MeshFilter then shows it instead of the particles.")]
         [SerializeField] Mesh visualMesh = null;
+        [Tooltip("The transform follows the body: after every FixedUpdate its position and rotation are set to the rigid frame that fits the deformed body best (SPEC.md 6f), so child objects, attached props, camera targets and audio sources move with it. The simulation keeps the frame the transform had at Start; the mesh is re-expressed in the moving frame on the CPU every tick.")]
+        [SerializeField] bool transformFollowsBody = false;
 
         // constraint graph (filled by an authoring script or SoftbodyMeshBuilder before Start)
         public Vector3[] restPositions;
@@ -84,10 +87,19 @@ namespace SoftbodyMI355X
         readonly SbRayHit[] hitBuffer = new SbRayHit[1];
         SbImpulse[] impulseQueue = new SbImpulse[16];      // AddImpulse / AddImpulseAtHit / AddExplosionImpulse since the last FixedUpdate, in call order
         int impulseCount;
+        // body state (SPEC.md 6f): what has been asked of the state the last tick left (bodyHas: BodyPose / BodyMotion bits), cached until the next tick or impulse
+        SbBodyState body;
+        uint bodyHas;
+        // The frame the simulation lives in. Without transformFollowsBody that is the component's transform, as it always was; with it the
+        // transform moves with the body, so the simulation keeps the frame the transform had at Start.
+        Matrix4x4 simToWorld = Matrix4x4.identity, worldToSim = Matrix4x4.identity;
+        Quaternion simRotation = Quaternion.identity;
+        Vector3[] shownPositions, shownNormals;     // transformFollowsBody: what the MeshFilter shows, in the moving frame
 
         void Start()
         {
             mesh = GetComponent<MeshFilter>().mesh;
+            simToWorld = transform.localToWorldMatrix; worldToSim = transform.worldToLocalMatrix; simRotation = transform.rotation;
             if (positions == null) { positions = mesh.vertices; restPositions = mesh.vertices; }
             int n = positions.Length;
             if (velocities == null) velocities = new Vector3[n];
@@ -211,6 +223,7 @@ namespace SoftbodyMI355X
         void FixedUpdate()
         {
             SendImpulses();      // everything queued since the last tick, in one call, before the step
+            bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
             {
                 // show the snapshot taken after the PREVIOUS tick (its copy and its normals ran beside this tick's kernels),
@@ -235,6 +248,7 @@ namespace SoftbodyMI355X
                     haveBounds = true;
                 }
                 snapshotPending = true;
+                if (transformFollowsBody) { FollowBody(); return; }
                 if (haveBounds)
                 {
                     // no rescan on the main thread: the box came with the snapshot. An empty or non-finite box (no rows, NaN or infinite
@@ -259,9 +273,116 @@ namespace SoftbodyMI355X
             {
                 cpu.Step(Time.fixedDeltaTime, substeps);
             }
+            if (transformFollowsBody) { FollowBody(); return; }
             mesh.vertices = positions;
             mesh.RecalculateNormals();
         }
+
+        /// <summary>transformFollowsBody: one POSE query (it peeks: the tick stays fusable), the transform set to the frame that fits the body best
+        /// -- the reference pose's origin and axes carried along, x = R (q - refCom) + com --, and the arrays on hand shown in that frame.
+        /// A degenerate or non-finite pose leaves the transform where it is.</summary>
+        void FollowBody()
+        {
+            SbBodyState s = QueryBody(SoftbodyNative.BodyPose);
+            var r = new Quaternion((float)s.rotationX, (float)s.rotationY, (float)s.rotationZ, (float)s.rotationW);
+            var com = new Vector3((float)s.comX, (float)s.comY, (float)s.comZ);
+            var refCom = new Vector3((float)s.refComX, (float)s.refComY, (float)s.refComZ);
+            Vector3 origin = com - r * refCom;
+            if ((s.flags & (SoftbodyNative.BodyNoMass | SoftbodyNative.BodyDegeneratePose)) == 0 && IsFinite(origin) && !float.IsNaN(r.x + r.y + r.z + r.w))
+                transform.SetPositionAndRotation(simToWorld.MultiplyPoint3x4(origin), simRotation * r);
+            Matrix4x4 simToLocal = transform.worldToLocalMatrix * simToWorld;
+            if (shownPositions == null || shownPositions.Length != positions.Length) shownPositions = new Vector3[positions.Length];
+            for (int i = 0; i < positions.Length; ++i) shownPositions[i] = simToLocal.MultiplyPoint3x4(positions[i]);
+            mesh.vertices = shownPositions;          // (Unity rescans the bounds: the box of the snapshot is in simulation space)
+            if (normals != null)
+            {
+                if (shownNormals == null || shownNormals.Length != normals.Length) shownNormals = new Vector3[normals.Length];
+                for (int i = 0; i < normals.Length; ++i) shownNormals[i] = simToLocal.MultiplyVector(normals[i]).normalized;
+                mesh.normals = shownNormals;
+            }
+            else mesh.RecalculateNormals();
+            if (tangents != null) mesh.RecalculateTangents();      // (the GPU's tangents are in simulation space)
+        }
+
+        /// <summary>The body state of what the last tick left (SPEC.md 6f), cached until the next tick: one call of sb_group_get_body_state per
+        /// tick and kind. Asking for MOTION completes the tick's held-back last kernel, so the next tick starts unfused (about what one
+        /// impulse costs); POSE alone peeks. The CPU branch adds the same 32 sums in C# and derives the fields with the plugin's pure function.</summary>
+        SbBodyState QueryBody(uint what)
+        {
+            if ((bodyHas & what) == what) return body;
+            what |= bodyHas;
+            if (handle != IntPtr.Zero)
+                SoftbodyNative.Check(SoftbodyNative.sb_group_get_body_state(handle, what, out body), "sb_group_get_body_state");
+            else
+            {
+                var sums = new double[32];
+                long nDynamic = 0, nPinned = 0;
+                Vector3[] rest = restPositions ?? positions;
+                for (int i = 0; i < inverseMass.Length; ++i)
+                {
+                    if (!(inverseMass[i] > 0f)) { ++nPinned; continue; }
+                    ++nDynamic;
+                    double m = 1.0 / (double)inverseMass[i];
+                    double x = positions[i].x, y = positions[i].y, z = positions[i].z;
+                    double a = rest[i].x, b = rest[i].y, c = rest[i].z;
+                    double d = velocities[i].x, e = velocities[i].y, f = velocities[i].z;
+                    sums[0] += m; sums[1] += m * x; sums[2] += m * y; sums[3] += m * z;
+                    sums[4] += m * a; sums[5] += m * b; sums[6] += m * c;
+                    sums[7] += m * x * x; sums[8] += m * y * y; sums[9] += m * z * z; sums[10] += m * x * y; sums[11] += m * x * z; sums[12] += m * y * z;
+                    sums[13] += m * x * a; sums[14] += m * x * b; sums[15] += m * x * c;
+                    sums[16] += m * y * a; sums[17] += m * y * b; sums[18] += m * y * c;
+                    sums[19] += m * z * a; sums[20] += m * z * b; sums[21] += m * z * c;
+                    sums[22] += m * d; sums[23] += m * e; sums[24] += m * f;
+                    sums[25] += m * (y * f - z * e); sums[26] += m * (z * d - x * f); sums[27] += m * (x * e - y * d);
+                    sums[28] += m * (d * d + e * e + f * f);
+                }
+                SoftbodyNative.Check(SoftbodyNative.sb_group_body_state_from_sums(sums, nDynamic, nPinned, what, out body), "sb_group_body_state_from_sums");
+            }
+            bodyHas = what;
+            return body;
+        }
+
+        /// <summary>Rigidbody.worldCenterOfMass for the soft body: the mass centre of the dynamic particles, world space (one POSE query per tick).</summary>
+        public Vector3 worldCenterOfMass
+        {
+            get { SbBodyState s = QueryBody(SoftbodyNative.BodyPose); return SimToWorldPoint(new Vector3((float)s.comX, (float)s.comY, (float)s.comZ)); }
+        }
+
+        /// <summary>transform.rotation for the soft body: the rotation that carries the reference pose onto the deformed body best (polar factor
+        /// of the mass-weighted pose covariance), world space. Identity for a degenerate pose (a single particle, particles on a line).</summary>
+        public Quaternion bodyRotation
+        {
+            get
+            {
+                SbBodyState s = QueryBody(SoftbodyNative.BodyPose);
+                return (transformFollowsBody ? simRotation : transform.rotation) * new Quaternion((float)s.rotationX, (float)s.rotationY, (float)s.rotationZ, (float)s.rotationW);
+            }
+        }
+
+        /// <summary>Rigidbody.velocity: momentum over mass, world space. A MOTION query: it costs the next tick its fused start.</summary>
+        public Vector3 velocity
+        {
+            get { SbBodyState s = QueryBody(SoftbodyNative.BodyMotion); return SimToWorldVector(new Vector3((float)s.velocityX, (float)s.velocityY, (float)s.velocityZ)); }
+        }
+
+        /// <summary>Rigidbody.angularVelocity: I^-1 L about the mass centre, radians per second, world space (a MOTION query). Zero for particles on a line.</summary>
+        public Vector3 angularVelocity
+        {
+            get
+            {
+                SbBodyState s = QueryBody(SoftbodyNative.BodyMotion);
+                return SimToWorldDirection(new Vector3((float)s.angularVelocityX, (float)s.angularVelocityY, (float)s.angularVelocityZ));
+            }
+        }
+
+        /// <summary>Half the sum of m |v|^2 over the dynamic particles, in the simulation's units (a MOTION query): "has it come to rest", impact audio.</summary>
+        public float kineticEnergy => (float)QueryBody(SoftbodyNative.BodyMotion).kineticEnergy;
+
+        Vector3 WorldToSimPoint(Vector3 p) => transformFollowsBody ? worldToSim.MultiplyPoint3x4(p) : transform.InverseTransformPoint(p);
+        Vector3 WorldToSimVector(Vector3 v) => transformFollowsBody ? worldToSim.MultiplyVector(v) : transform.InverseTransformVector(v);
+        Vector3 SimToWorldPoint(Vector3 p) => transformFollowsBody ? simToWorld.MultiplyPoint3x4(p) : transform.TransformPoint(p);
+        Vector3 SimToWorldVector(Vector3 v) => transformFollowsBody ? simToWorld.MultiplyVector(v) : transform.TransformVector(v);
+        Vector3 SimToWorldDirection(Vector3 d) => transformFollowsBody ? simRotation * d : transform.TransformDirection(d);
 
         static bool IsFinite(Vector3 v)
         {
@@ -283,7 +404,7 @@ namespace SoftbodyMI355X
         {
             hit = default(SoftbodyHit);
             if (handle == IntPtr.Zero || hitTriangles == null || !haveBounds) return false;      // (haveBounds: a snapshot has ended)
-            Vector3 o = transform.InverseTransformPoint(ray.origin), d = transform.InverseTransformVector(ray.direction);      // t stays a world distance
+            Vector3 o = WorldToSimPoint(ray.origin), d = WorldToSimVector(ray.direction);      // t stays a world distance
             rayBuffer[0] = o.x; rayBuffer[1] = o.y; rayBuffer[2] = o.z; rayBuffer[3] = maxDistance;
             rayBuffer[4] = d.x; rayBuffer[5] = d.y; rayBuffer[6] = d.z; rayBuffer[7] = 0f;
             SoftbodyNative.Check(SoftbodyNative.sb_group_readback_raycast(handle, rayBuffer, 1, hitBuffer), "sb_group_readback_raycast");
@@ -292,10 +413,10 @@ namespace SoftbodyMI355X
             int a = hitTriangles[3 * h.triangle], b = hitTriangles[3 * h.triangle + 1], c = hitTriangles[3 * h.triangle + 2];
             float wa = 1f - h.u - h.v;
             hit.triangle = h.triangle; hit.distance = h.t; hit.barycentric = new Vector3(wa, h.u, h.v);
-            hit.point = transform.TransformPoint(wa * positions[a] + h.u * positions[b] + h.v * positions[c]);
+            hit.point = SimToWorldPoint(wa * positions[a] + h.u * positions[b] + h.v * positions[c]);
             Vector3 nrm = normals != null ? wa * normals[a] + h.u * normals[b] + h.v * normals[c]
                                           : Vector3.Cross(positions[b] - positions[a], positions[c] - positions[a]);
-            hit.normal = transform.TransformDirection(nrm).normalized;
+            hit.normal = SimToWorldDirection(nrm).normalized;
             return true;
         }
 
@@ -304,7 +425,7 @@ namespace SoftbodyMI355X
         public void AddImpulse(int particle, Vector3 impulse, bool velocityChange = false)
         {
             if (particle < 0 || particle >= inverseMass.Length) throw new ArgumentOutOfRangeException(nameof(particle));
-            Vector3 j = transform.InverseTransformVector(impulse);
+            Vector3 j = WorldToSimVector(impulse);
             Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_PARTICLE, flags = velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u,
                                   index = particle, vecX = j.x, vecY = j.y, vecZ = j.z });
         }
@@ -313,7 +434,7 @@ namespace SoftbodyMI355X
         /// barycentric weights (with a visual mesh: on to the cage particles behind each corner, by the skinning weights).</summary>
         public void AddImpulseAtHit(SoftbodyHit hit, Vector3 impulse, bool velocityChange = false)
         {
-            Vector3 j = transform.InverseTransformVector(impulse);
+            Vector3 j = WorldToSimVector(impulse);
             Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_SURFACE, flags = velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u,
                                   index = hit.triangle, u = hit.barycentric.y, v = hit.barycentric.z, vecX = j.x, vecY = j.y, vecZ = j.z });
         }
@@ -323,7 +444,7 @@ namespace SoftbodyMI355X
         /// inwards. The radius is taken in the component's local space.</summary>
         public void AddExplosionImpulse(float strength, Vector3 centre, float radius, bool linearFalloff = true, bool velocityChange = false)
         {
-            Vector3 c = transform.InverseTransformPoint(centre);
+            Vector3 c = WorldToSimPoint(centre);
             Queue(new SbImpulse { kind = SoftbodyNative.SB_IMPULSE_RADIAL,
                                   flags = (linearFalloff ? SoftbodyNative.SB_IMPULSE_LINEAR_FALLOFF : 0u) | (velocityChange ? SoftbodyNative.SB_IMPULSE_VELOCITY_CHANGE : 0u),
                                   vecX = c.x, vecY = c.y, vecZ = c.z, radius = radius, strength = strength });
@@ -340,6 +461,7 @@ namespace SoftbodyMI355X
             if (impulseCount == 0) return;
             int count = impulseCount;
             impulseCount = 0;                                // (an error drops the batch instead of repeating it every tick)
+            bodyHas = 0;
             if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_impulses(handle, impulseQueue, count), "sb_group_apply_impulses");
             else if (cpu != null) cpu.ApplyImpulses(impulseQueue, count, renderTriangles);
         }

@@ -137,6 +137,29 @@ namespace SoftbodyMI355X
         public int reserved0, reserved1;
     }
 
+    /// <summary>sb_body_state (592 bytes): what sb_group_get_body_state / sb_group_body_state_from_sums fill (SPEC.md 6f). what = SoftbodyNative.BodyPose |
+    /// BodyMotion as asked, flags = BodyNoMass | BodyDegeneratePose | BodyDegenerateInertia. sums: the 32 mass-weighted sums in binary64 (the header lists the slots);
+    /// secondMoment about com (xx, yy, zz, xy, xz, yz); apq row-major; rotation: unit quaternion (x, y, z, w), w >= 0, reference pose -> simulation space;
+    /// angularMomentum about com. Fields that were not asked for are 0, the rotation then identity.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbBodyState
+    {
+        public long nDynamic, nPinned;
+        public uint what, flags;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 32)] public double[] sums;
+        public double mass;
+        public double comX, comY, comZ;
+        public double refComX, refComY, refComZ;
+        public double secondMomentXX, secondMomentYY, secondMomentZZ, secondMomentXY, secondMomentXZ, secondMomentYZ;
+        public double apq00, apq01, apq02, apq10, apq11, apq12, apq20, apq21, apq22;
+        public double rotationX, rotationY, rotationZ, rotationW;
+        public double momentumX, momentumY, momentumZ;
+        public double velocityX, velocityY, velocityZ;
+        public double angularMomentumX, angularMomentumY, angularMomentumZ;
+        public double angularVelocityX, angularVelocityY, angularVelocityZ;
+        public double kineticEnergy;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -156,6 +179,10 @@ namespace SoftbodyMI355X
         public const int ScheduleAuto = 0, ScheduleSerialEager = 1, ScheduleSerialGraph = 2, ScheduleOverlapEager = 3, ScheduleOverlapGraph = 4;
         public const uint GroupWalk = 1;       // sb_group_create flags: no plugin threads, the calling thread walks the tick across the ranks
         public const uint GroupWholeMesh = 2;  // never cut windows: every rank plans the whole mesh (sb_group_finalize)
+        // sb_group_get_body_state (SPEC.md 6f): what to ask for, and sb_body_state.flags
+        public const uint BodyPose = 1;        // positions only: peeks, the tick stays fusable
+        public const uint BodyMotion = 2;      // needs velocities: completes the tick's held-back last kernel
+        public const uint BodyNoMass = 1, BodyDegeneratePose = 2, BodyDegenerateInertia = 4;
         // sb_impulse (SPEC.md 2c), named as in include/softbody.h
         public const int SB_IMPULSE_PARTICLE = 0, SB_IMPULSE_SURFACE = 1, SB_IMPULSE_RADIAL = 2;      // SbImpulse.kind
         public const uint SB_IMPULSE_VELOCITY_CHANGE = 1, SB_IMPULSE_LINEAR_FALLOFF = 2;               // SbImpulse.flags (LINEAR_FALLOFF: RADIAL only)
@@ -263,6 +290,8 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_raycast(IntPtr g, float[] rays, int count, [Out] SbRayHit[] hits);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_rank_count(IntPtr g);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_rank(IntPtr g, int rank, out IntPtr solver);

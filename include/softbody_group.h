@@ -125,6 +125,44 @@ int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
  * device, on the gathered snapshot (whole array or render set) or the skinned vertices, in both host models -- the ranks take no part. */
 int sb_group_readback_raycast(sb_group *g, const float *rays /* 8 floats per ray */, int32_t count, sb_ray_hit *hits_out);
 
+/* ---- body state: where the body is and how it moves (SPEC.md 6f) ------------------------------------------------------------------------- */
+/* What Rigidbody.worldCenterOfMass / .velocity / .angularVelocity and transform.position / rotation are to a rigid body, for a soft one:
+ * mass centre, momenta, kinetic energy and the rigid frame that fits the deformed body best -- a few hundred bytes instead of the state.
+ * Every rank reduces the DYNAMIC particles it owns (inverse mass > 0; pinned ones are only counted) to 32 mass-weighted sums in binary64 on
+ * its own device, two launches and no atomics; the host adds the ranks' sums in rank order and derives the fields below from the totals.
+ * The sums depend on the device order of the particles, so SPEC.md 6f gives them an error bound and run-to-run determinism, not bits:
+ * two calls on the same state return the same bits. Non-finite inputs propagate by IEEE rules.
+ * sums[]: 0 mass; 1..3 sum m x; 4..6 sum m q; 7..12 sum m x x^T (xx, yy, zz, xy, xz, yz); 13..21 sum m x q^T (row = component of x);
+ * 22..24 sum m v; 25..27 sum m (x cross v); 28 sum m |v|^2; 29..31 zero -- x, v the tick-end state, q the reference pose (what
+ * sb_group_set_rest_positions gave, else the positions of sb_group_set_particles), all about the world origin. A slot and a field that
+ * `what` did not ask for are 0, the rotation then identity. POSE gives slots 0..21, MOTION 0..3, 7..12 and 22..28. */
+#define SB_BODY_POSE   1u   /* positions only: peeks where sb_group_get_bounds peeks; the tick stays fusable */
+#define SB_BODY_MOTION 2u   /* needs velocities: completes the tick's held-back last kernel, as sb_group_get_velocities does */
+/* sb_body_state.flags */
+#define SB_BODY_NO_MASS            1u   /* no dynamic particle: every field 0, rotation identity */
+#define SB_BODY_DEGENERATE_POSE    2u   /* apq has rank below 2 (sigma_2 <= 1e-12 sigma_1: one particle, collinear poses): rotation identity */
+#define SB_BODY_DEGENERATE_INERTIA 4u   /* inertia tensor with lambda_min <= 1e-12 lambda_max (collinear particles, fewer than 3): angular_velocity 0 */
+
+typedef struct {
+    int64_t n_dynamic, n_pinned;
+    uint32_t what, flags;
+    double sums[32];
+    double mass, com[3], ref_com[3], second_moment[6], apq[9], rotation[4];     /* second_moment about com, in the order of slots 7..12;
+                                                                                    apq = sum m (x - com)(q - ref_com)^T, row-major;
+                                                                                    rotation: unit quaternion (x, y, z, w), w >= 0, of the
+                                                                                    polar factor of apq with det = +1 (reference -> world) */
+    double momentum[3], velocity[3], angular_momentum[3], angular_velocity[3], kinetic_energy;    /* angular_momentum about com;
+                                                                                    angular_velocity = I^-1 L, I = tr(C) 1 - C */
+} sb_body_state;
+
+/* Synchronous, like sb_group_get_bounds, in both host models. SB_ERR_INVALID_ARG (null argument, what == 0, an unknown bit) leaves *out
+ * untouched; SB_ERR_STATE before sb_group_finalize. The first POSE query uploads the reference pose (12 bytes per owned particle) and the
+ * first query of any kind allocates the workgroups' rows; until then sb_stats.device_bytes is what it was. */
+int sb_group_get_body_state(sb_group *g, uint32_t what, sb_body_state *out);
+/* Pure: no group, no GPU. A host adds the sums[] of several bodies (and their counts) and derives the compound body's state; slots `what`
+ * does not cover are ignored. SB_ERR_INVALID_ARG as above, or for a negative count. */
+int sb_group_body_state_from_sums(const double sums[32], int64_t n_dynamic, int64_t n_pinned, uint32_t what, sb_body_state *out);
+
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);
 int32_t sb_group_rank_count(const sb_group *g);

@@ -494,6 +494,14 @@ int finalize_link(sb_solver *s) {
             }
         }
         HIP_CHECK(hipDeviceSynchronize());
+        // the reference pose of the owned particles, in device order: what a body-state query (SPEC.md 6f) uploads at its first use
+        {
+            const std::vector<float> &rp = s->rest.empty() ? s->pos : s->rest;
+            const std::vector<int32_t> &l2o = s->plan->local.local_to_old;
+            s->ref_pose.resize((size_t)s->n_owned * 3);
+            for (int64_t l = 0; l < s->n_owned; ++l)
+                for (int c = 0; c < 3; ++c) s->ref_pose[3 * (size_t)l + c] = rp[3 * (size_t)l2o[(size_t)l] + c];
+        }
         // authoring copies are no longer needed (keep rest values out of memory for 50M-constraint meshes)
         std::vector<float>().swap(s->pos); std::vector<float>().swap(s->vel); std::vector<float>().swap(s->rest);
         std::vector<int32_t>().swap(s->dist_ij); std::vector<int32_t>().swap(s->vol_ijkl); std::vector<int32_t>().swap(s->bend_ijkl);

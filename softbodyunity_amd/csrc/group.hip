@@ -875,6 +875,26 @@ int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]) {
     return SB_OK;
 }
 
+int sb_group_get_body_state(sb_group *g, uint32_t what, sb_body_state *out) {
+    if (!g || !out) return fail(SB_ERR_INVALID_ARG, "sb_group_get_body_state: null argument");
+    if (what == 0 || (what & ~(SB_BODY_POSE | SB_BODY_MOTION))) return fail(SB_ERR_INVALID_ARG, "sb_group_get_body_state: `what` must be SB_BODY_POSE, SB_BODY_MOTION or both");
+    if (int rc = check_group(g, true, "sb_group_get_body_state")) return rc;
+    // every rank reduces what it owns on its own device (272 bytes each to the host); the ranks' sums are added in rank order, so the
+    // same state gives the same bits (SPEC.md 6f), and everything else is derived from the totals
+    std::vector<std::array<double, 32>> sums((size_t)g->W);
+    std::vector<std::array<int64_t, 2>> counts((size_t)g->W);
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return get_body_sums_owned(g->ranks[(size_t)r], what, sums[(size_t)r].data(), counts[(size_t)r].data()); }); });
+    if (rc) return rc;
+    std::array<double, 32> total = sums[0];
+    int64_t n_dynamic = counts[0][0], n_pinned = counts[0][1];
+    for (int r = 1; r < g->W; ++r) {
+        for (size_t k = 0; k < 32; ++k) total[k] += sums[(size_t)r][k];
+        n_dynamic += counts[(size_t)r][0]; n_pinned += counts[(size_t)r][1];
+    }
+    body_state_derive(total.data(), n_dynamic, n_pinned, what, out);
+    return SB_OK;
+}
+
 int sb_group_readback_raycast(sb_group *g, const float *rays, int32_t count, sb_ray_hit *hits_out) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_raycast: null group");
     return guarded([&]() -> int {

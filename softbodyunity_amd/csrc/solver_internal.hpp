@@ -3,7 +3,7 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
-// tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
+// tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
@@ -292,6 +292,13 @@ struct sb_solver {
     int peek_min_tiles = 2048;
     int64_t n_peeks = 0;                   // launches so far (sb_stats.readback_peeks)
     int64_t n_fused = 0;                   // ticks that started with the fused kernel (sb_stats.ticks_fused)
+    // Body state (sb_group_get_body_state, body_state.hip; SPEC.md 6f): the reference pose of the owned particles in device order -- kept on
+    // the host by sb_finalize (12 bytes per owned particle) and moved to the device by the first POSE query --, the workgroups' rows and
+    // the mapped pinned row the final kernel writes (32 sums, 2 counts), both from the first query on
+    std::vector<float> ref_pose;
+    DevBuf<float> d_ref_pose;
+    DevBuf<double> d_body_partials;
+    sbi::HostBuf<double> h_body;
 
     // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
     // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
@@ -351,6 +358,13 @@ int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t co
 const float *tick_end_positions(sb_solver *s, bool subset = false, const std::vector<int32_t> &wanted_local = {});
 // sb_get_bounds: the box of the particles this rank owns, on what sb_get_positions would return now (peeks where that peeks)
 int get_bounds_owned(sb_solver *s, float lo[3], float hi[3]);
+
+// ---- body_state.hip: mass centre, momenta, best-fit rotation (SPEC.md 6f) ------------------------------------------------------------------
+// the 32 sums over the particles this rank owns (what = SB_BODY_POSE | SB_BODY_MOTION bits; counts = dynamic, pinned): POSE alone peeks
+// where get_bounds_owned peeks, MOTION completes the tick's held-back last kernel as a velocity read does
+int get_body_sums_owned(sb_solver *s, uint32_t what, double sums[32], int64_t counts[2]);
+// every field of *out from the sums (pure host arithmetic; the arguments are valid)
+void body_state_derive(const double sums[32], int64_t n_dynamic, int64_t n_pinned, uint32_t what, sb_body_state *out);
 
 // ---- impulse.hip: impulses between two ticks (SPEC.md 2c) ----------------------------------------------------------------------------------
 int64_t impulse_triangles_in_force(const RenderState &R);       // triangles of the render mode in force, -1 = none

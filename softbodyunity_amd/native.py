@@ -31,6 +31,8 @@ SB_GROUP_WHOLE_MESH = 2
  SB_TUNE_NO_WIDE_SLOTS, SB_TUNE_AUTO_PREFER_OVERLAP, SB_TUNE_NO_AUTO_CALIBRATION, SB_TUNE_NO_SHARED_PROGRAMS) = (1 << k for k in range(16))
 SB_IMPULSE_PARTICLE, SB_IMPULSE_SURFACE, SB_IMPULSE_RADIAL = 0, 1, 2
 SB_IMPULSE_VELOCITY_CHANGE, SB_IMPULSE_LINEAR_FALLOFF = 1, 2
+SB_BODY_POSE, SB_BODY_MOTION = 1, 2
+SB_BODY_NO_MASS, SB_BODY_DEGENERATE_POSE, SB_BODY_DEGENERATE_INERTIA = 1, 2, 4
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -110,6 +112,23 @@ class SbImpulse(C.Structure):
     """sb_impulse (48 bytes): one item of sb_apply_impulses (SPEC.md 2c)"""
     _fields_ = [("kind", C.c_int32), ("flags", C.c_uint32), ("index", C.c_int32), ("u", C.c_float), ("v", C.c_float),
                 ("vec", C.c_float * 3), ("radius", C.c_float), ("strength", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class SbBodyState(C.Structure):
+    """sb_body_state (592 bytes): what sb_group_get_body_state / sb_group_body_state_from_sums fill (SPEC.md 6f)"""
+    _fields_ = [("n_dynamic", C.c_int64), ("n_pinned", C.c_int64), ("what", C.c_uint32), ("flags", C.c_uint32), ("sums", C.c_double * 32),
+                ("mass", C.c_double), ("com", C.c_double * 3), ("ref_com", C.c_double * 3), ("second_moment", C.c_double * 6),
+                ("apq", C.c_double * 9), ("rotation", C.c_double * 4), ("momentum", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("angular_momentum", C.c_double * 3), ("angular_velocity", C.c_double * 3), ("kinetic_energy", C.c_double)]
+
+    def as_dict(self):
+        """scalars as Python numbers, arrays as float64 numpy arrays (apq as 3 x 3)"""
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = np.array(v[:], np.float64) if hasattr(v, "__len__") else v
+        out["apq"] = out["apq"].reshape(3, 3)
+        return out
 
 
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
@@ -216,6 +235,8 @@ SIGNATURES = {
     "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
+    "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
+    "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),
     "sb_group_rank_count": (C.c_int32, [_P]),
     "sb_group_get_rank": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

@@ -589,6 +589,13 @@ class SoftbodyGroup:
         """-> (lo, hi): every rank's box of what it owns, combined on the host."""
         return _box(native.lib().sb_group_get_bounds, self._g)
 
+    def get_body_state(self, what=native.SB_BODY_POSE | native.SB_BODY_MOTION):
+        """-> dict of sb_body_state's fields (SPEC.md 6f): mass centre, momenta, kinetic energy, best-fit rotation as a quaternion
+        (x, y, z, w). what = SB_BODY_POSE (peeks: the tick stays fusable), SB_BODY_MOTION (completes the tick) or both."""
+        st = native.SbBodyState()
+        check(native.lib().sb_group_get_body_state(self._g, int(what), C.byref(st)))
+        return st.as_dict()
+
     def _rank_handle(self, r):
         h = C.c_void_p()
         check(native.lib().sb_group_get_rank(self._g, int(r), C.byref(h)))
