@@ -98,62 +98,37 @@ int sb_destroy(sb_solver *s) {
 }
 
 int sb_set_particles(sb_solver *s, const float *pos, const float *vel, const float *inv_mass, int32_t n) {
-    if (!s || !pos || !inv_mass || n <= 0) return fail(SB_ERR_INVALID_ARG, "sb_set_particles: bad argument");
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_particles: bad argument");
     if (s->finalized) return fail(SB_ERR_STATE, "sb_set_particles after sb_finalize");
-    return guarded([&]() -> int {
-        for (int32_t p = 0; p < n; ++p) if (!(inv_mass[p] >= 0.0f)) return fail(SB_ERR_INVALID_ARG, "sb_set_particles: inverse mass must be >= 0");
-        s->n = n;
-        s->pos.assign(pos, pos + 3 * (size_t)n);
-        if (vel) s->vel.assign(vel, vel + 3 * (size_t)n); else s->vel.assign(3 * (size_t)n, 0.0f);
-        s->invm.assign(inv_mass, inv_mass + n);
-        return SB_OK;
-    });
+    return guarded([&]() -> int { return report(s->mesh->set_particles("sb_set_particles", pos, vel, inv_mass, n)); });
 }
 
 int sb_set_rest_positions(sb_solver *s, const float *rest, int32_t n) {
-    if (!s || !rest) return fail(SB_ERR_INVALID_ARG, "sb_set_rest_positions: bad argument");
+    if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_rest_positions: bad argument");
     if (s->finalized) return fail(SB_ERR_STATE, "sb_set_rest_positions after sb_finalize");
-    if (n != s->n) return fail(SB_ERR_INVALID_ARG, "sb_set_rest_positions: n differs from sb_set_particles");
-    return guarded([&]() -> int { s->rest.assign(rest, rest + 3 * (size_t)n); return SB_OK; });
+    return guarded([&]() -> int { return report(s->mesh->set_rest_positions("sb_set_rest_positions", rest, n)); });
 }
 
-static int set_cons(sb_solver *s, const char *who, const int32_t *idx, const float *rest, int32_t m, float compliance,
-                    int type, int nv, int nrest) {
-    if (!s || m < 0 || (m > 0 && (!idx || !rest))) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": bad argument");
+static int set_cons(sb_solver *s, const char *who, int type, const int32_t *idx, const float *rest, int32_t m, float compliance) {
+    if (!s) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": bad argument");
     if (s->finalized) return fail(SB_ERR_STATE, std::string(who) + " after sb_finalize");
-    if (s->n <= 0) return fail(SB_ERR_STATE, std::string(who) + " before sb_set_particles");
-    if (!(compliance >= 0.0f)) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": compliance must be >= 0");
-    return guarded([&]() -> int {
-        std::atomic<bool> bad{false};
-        sbp::parallel_for_chunks((int64_t)m * nv, 1 << 22, [&](int64_t, int64_t kb, int64_t ke) {
-            for (int64_t k = kb; k < ke; ++k) if (idx[k] < 0 || idx[k] >= s->n) { bad = true; return; }
-        });
-        if (bad) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": particle index out of range");
-        std::vector<int32_t> &I = type == 0 ? s->dist_ij : (type == 1 ? s->vol_ijkl : s->bend_ijkl);
-        std::vector<float> &R = type == 0 ? s->dist_rest : (type == 1 ? s->vol_rest : s->bend_rest);
-        I.assign(idx, idx + (size_t)m * nv);
-        R.assign(rest, rest + (size_t)m * nrest);
-        s->compliance[type] = compliance;
-        return SB_OK;
-    });
+    return guarded([&]() -> int { return report(s->mesh->set_constraints(type, who, idx, rest, m, compliance)); });
 }
 
 int sb_set_distance_constraints(sb_solver *s, const int32_t *ij, const float *rest_len, int32_t m, float compliance) {
-    return set_cons(s, "sb_set_distance_constraints", ij, rest_len, m, compliance, 0, 2, 1);
+    return set_cons(s, "sb_set_distance_constraints", 0, ij, rest_len, m, compliance);
 }
 int sb_set_volume_constraints(sb_solver *s, const int32_t *ijkl, const float *rest_vol, int32_t m, float compliance) {
-    return set_cons(s, "sb_set_volume_constraints", ijkl, rest_vol, m, compliance, 1, 4, 1);
+    return set_cons(s, "sb_set_volume_constraints", 1, ijkl, rest_vol, m, compliance);
 }
 int sb_set_bending_constraints(sb_solver *s, const int32_t *ijkl, const float *rest_cs, int32_t m, float compliance) {
-    return set_cons(s, "sb_set_bending_constraints", ijkl, rest_cs, m, compliance, 2, 4, 2);
+    return set_cons(s, "sb_set_bending_constraints", 2, ijkl, rest_cs, m, compliance);
 }
 
 int sb_set_ground_plane(sb_solver *s, float nx, float ny, float nz, float d, int32_t enabled) {
     if (!s) return fail(SB_ERR_INVALID_ARG, "sb_set_ground_plane: null handle");
-    if (!(nx == nx) || !(ny == ny) || !(nz == nz) || !(d == d)) return fail(SB_ERR_INVALID_ARG, "sb_set_ground_plane: NaN");
-    s->plane[0] = nx; s->plane[1] = ny; s->plane[2] = nz; s->plane[3] = d;
-    s->plane_on = enabled ? 1 : 0;
-    return SB_OK;   // picked up by the next sb_step (tick parameters are re-uploaded when they change)
+    // picked up by the next sb_step (tick parameters are re-uploaded when they change)
+    return report(s->mesh->set_ground_plane("sb_set_ground_plane", nx, ny, nz, d, enabled));
 }
 
 int sb_comm_unique_id(uint8_t out_id[SB_UNIQUE_ID_BYTES]) {
@@ -225,7 +200,7 @@ int sb_peer_connect(sb_solver *s, int32_t rank, const uint8_t handle[SB_IPC_HAND
 int sb_set_domain(sb_solver *s, const sb_domain *domain, const int32_t *global_id, int32_t n) {
     if (!s || !domain || !global_id) return fail(SB_ERR_INVALID_ARG, "sb_set_domain: null argument");
     if (s->finalized) return fail(SB_ERR_STATE, "sb_set_domain after sb_finalize");
-    if (n != s->n || n <= 0) return fail(SB_ERR_INVALID_ARG, "sb_set_domain: n differs from sb_set_particles");
+    if (n != s->mesh->n || n <= 0) return fail(SB_ERR_INVALID_ARG, "sb_set_domain: n differs from sb_set_particles");
     if (domain->n_global < n || !(domain->spacing > 0) || domain->reserved != 0) return fail(SB_ERR_INVALID_ARG, "sb_set_domain: bad domain");
     return guarded([&]() -> int {
         s->domain = *domain;
@@ -238,15 +213,7 @@ int sb_set_domain(sb_solver *s, const sb_domain *domain, const int32_t *global_i
 int sb_domain_from_mesh(const float *rest, int32_t n, const int32_t *dist_ij, int32_t m_d, const int32_t *vol, int32_t m_v,
                         const int32_t *bend, int32_t m_b, sb_domain *out) {
     if (!rest || !out || n <= 0 || m_d < 0 || m_v < 0 || m_b < 0) return fail(SB_ERR_INVALID_ARG, "sb_domain_from_mesh: bad argument");
-    return guarded([&]() -> int {
-        sbp::Domain D;
-        sbp::compute_domain(make_input(rest, n, dist_ij, m_d, vol, m_v, bend, m_b), D);
-        std::memset(out, 0, sizeof(*out));
-        out->n_global = D.n_global; out->spacing = D.ell; out->fill = D.fill;
-        for (int a = 0; a < 3; ++a) { out->lo[a] = D.lo[a]; out->hi[a] = D.hi[a]; }
-        out->four_vertex_constraints = (m_v + m_b > 0) ? 1 : 0;
-        return SB_OK;
-    });
+    return guarded([&]() -> int { *out = domain_of(make_input(rest, n, dist_ij, m_d, vol, m_v, bend, m_b)); return SB_OK; });
 }
 
 int sb_domain_window(const sb_domain *domain, const sb_plan_opts *opts, double lo_out[3], double hi_out[3]) {
@@ -263,6 +230,16 @@ int sb_domain_window(const sb_domain *domain, const sb_plan_opts *opts, double l
 }  // extern "C"  (the phases of sb_finalize are shared with group.hip)
 
 namespace sbi {
+
+sb_domain domain_of(const sbp::Input &in) {
+    sbp::Domain D;
+    sbp::compute_domain(in, D);
+    sb_domain out{};
+    out.n_global = D.n_global; out.spacing = D.ell; out.fill = D.fill;
+    for (int a = 0; a < 3; ++a) { out.lo[a] = D.lo[a]; out.hi[a] = D.hi[a]; }
+    out.four_vertex_constraints = (in.m_v + in.m_b > 0) ? 1 : 0;
+    return out;
+}
 
 // Phase A of sb_finalize: everything a rank does ALONE -- resolve the schedule and plan (finalize_plan: host work only), then build and
 // upload the device tables (finalize_device). No collective, no look at a neighbour. Throws / returns an error code like any guarded
@@ -306,9 +283,7 @@ int finalize_plan(sb_solver *s) {
                         "exchange stream); this process is bound to HIP runtime " + std::to_string(hip_runtime_version()) +
                         " (a host that loaded PyTorch first runs on PyTorch's bundled runtime): use SB_SCHEDULE_SERIAL_GRAPH or an eager schedule");
     }
-    const std::vector<float> &rest = s->rest.empty() ? s->pos : s->rest;
-    sbp::Input in = make_input(rest.data(), s->n, s->dist_ij.data(), (int64_t)s->dist_rest.size(), s->vol_ijkl.data(),
-                               (int64_t)s->vol_rest.size(), s->bend_ijkl.data(), (int64_t)s->bend_rest.size() / 2);
+    sbp::Input in = make_input(*s->mesh);
     if (s->sharded) {
         if (s->desc.world < 2) return fail(SB_ERR_INVALID_ARG, "sb_finalize: sharded authoring (sb_set_domain) is for world > 1");
         if (s->desc.partition == SB_PARTITION_RCB) return fail(SB_ERR_UNSUPPORTED, "sb_finalize: the RCB partition needs the whole mesh on every rank (no sb_set_domain)");
@@ -496,16 +471,16 @@ int finalize_link(sb_solver *s) {
         HIP_CHECK(hipDeviceSynchronize());
         // the reference pose of the owned particles, in device order: what a body-state query (SPEC.md 6f) uploads at its first use
         {
-            const std::vector<float> &rp = s->rest.empty() ? s->pos : s->rest;
+            const std::vector<float> &rp = s->mesh->rest_or_pos();
             const std::vector<int32_t> &l2o = s->plan->local.local_to_old;
             s->ref_pose.resize((size_t)s->n_owned * 3);
             for (int64_t l = 0; l < s->n_owned; ++l)
                 for (int c = 0; c < 3; ++c) s->ref_pose[3 * (size_t)l + c] = rp[3 * (size_t)l2o[(size_t)l] + c];
         }
-        // authoring copies are no longer needed (keep rest values out of memory for 50M-constraint meshes)
-        std::vector<float>().swap(s->pos); std::vector<float>().swap(s->vel); std::vector<float>().swap(s->rest);
-        std::vector<int32_t>().swap(s->dist_ij); std::vector<int32_t>().swap(s->vol_ijkl); std::vector<int32_t>().swap(s->bend_ijkl);
-        std::vector<float>().swap(s->dist_rest); std::vector<float>().swap(s->vol_rest); std::vector<float>().swap(s->bend_rest);
+        // the authored arrays are no longer needed: dropped in place, or -- the whole mesh a group's ranks share, the group still holding
+        // it -- left to the others, with this rank's own copy of what is read after finalize
+        if (s->mesh.use_count() == 1) s->mesh->release_bulk();
+        else s->mesh = std::make_shared<AuthoredMesh>(s->mesh->without_bulk());
         s->finalized = true;
         return SB_OK;
     });
@@ -518,7 +493,7 @@ extern "C" {
 int sb_finalize(sb_solver *s) {
     if (!s) return fail(SB_ERR_INVALID_ARG, "sb_finalize: null handle");
     if (s->finalized) return fail(SB_ERR_STATE, "sb_finalize called twice");
-    if (s->n <= 0) return fail(SB_ERR_STATE, "sb_finalize before sb_set_particles");
+    if (s->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_finalize before sb_set_particles");
     const bool no_comm = (s->desc.debug_flags & SB_DEBUG_NO_COMM) != 0;
     if (s->desc.world > 1 && !s->comm && !s->peer.enabled && !no_comm)
         return fail(SB_ERR_STATE, "sb_finalize: world > 1 needs sb_comm_init first (or halo_transport = SB_TRANSPORT_PEER with sb_peer_connect)");
@@ -546,7 +521,7 @@ int sb_synchronize(sb_solver *s) {
 int sb_get_owner(sb_solver *s, int32_t *owner, int32_t n) {
     if (!s || !owner) return fail(SB_ERR_INVALID_ARG, "sb_get_owner: null argument");
     if (!s->finalized) return fail(SB_ERR_STATE, "sb_get_owner before sb_finalize");
-    if (n != s->n) return fail(SB_ERR_INVALID_ARG, "sb_get_owner: n mismatch");
+    if (n != s->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_get_owner: n mismatch");
     std::memcpy(owner, s->plan->plan.owner_of_old.data(), (size_t)n * sizeof(int32_t));
     return SB_OK;
 }

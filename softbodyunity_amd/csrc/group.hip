@@ -86,18 +86,8 @@ struct sb_group {
     std::vector<sb_solver *> ranks;
     std::unique_ptr<RankThreads> threads;       // null in walk mode (and for a single rank)
     bool finalized = false, sharded = false;
-    // the mesh, authored once
-    int32_t n = 0;
-    std::vector<float> pos, vel, invm, rest;
-    std::vector<int32_t> dist_ij, vol_ijkl, bend_ijkl;
-    std::vector<float> dist_rest, vol_rest, bend_rest;
-    float compliance[3] = {0, 0, 0};
-    float plane[4] = {0, 1, 0, 0};
-    int32_t plane_on = 0;
-    bool plane_set = false;
-    std::vector<uint8_t> pinned;                 // [n] inverse mass == 0 (kept for sb_group_set_kinematic_positions)
-    // per rank: the rank's numbering -> the caller's (sharded authoring: window index -> whole-mesh id; empty = identity)
-    std::vector<std::vector<int32_t>> gid;
+    // the mesh, authored once (authoring.hpp): the ranks are handed windows cut from it, or share it
+    std::shared_ptr<AuthoredMesh> mesh = std::make_shared<AuthoredMesh>();
     // kinematic scratch per rank (ids in the rank's numbering)
     std::vector<std::vector<int32_t>> kin_ids;
     std::vector<std::vector<float>> kin_pos;
@@ -148,82 +138,29 @@ namespace {
 
 bool walk_mode(const sb_group *g) { return (g->flags & SB_GROUP_WALK) != 0 || g->W == 1; }
 
-// The window of the whole mesh rank r hands over under sharded authoring: the particles whose rest position lies in its box, the
-// constraints among them in the whole mesh's order, the particles' whole-mesh ids (ascending).
-struct Window {
-    std::vector<int32_t> gid;
-    std::vector<float> pos, vel, invm, rest;
-    std::vector<int32_t> idx[3];
-    std::vector<float> restv[3];
-};
-void cut_window(const sb_group *g, const sb_domain &dom, int r, Window &w) {
+// The mesh to rank r: its window of the whole mesh under sharded authoring (the particles whose rest position lies in its box, the
+// constraints among them; their whole-mesh ids, domain and `sharded` as sb_set_domain sets them), else the group's mesh itself.
+int author_rank(sb_group *g, int r, const sb_domain *dom) {
+    sb_solver *s = g->ranks[(size_t)r];
+    if (!dom) { s->mesh = g->mesh; return SB_OK; }
     sb_plan_opts o{};
     o.rank = r; o.world = g->W;
     for (int a = 0; a < 3; ++a) o.part_dims[a] = g->desc.part_dims[a];
     // (the automatic tile size must be resolved the way plan_opts resolves it for the whole mesh)
     o.tile_particles = g->desc.tile_particles;
     double lo[3], hi[3];
-    if (sb_domain_window(&dom, &o, lo, hi) != SB_OK) throw std::runtime_error(std::string("sb_group_finalize: ") + last_error_text());
-    const std::vector<float> &rp = g->rest.empty() ? g->pos : g->rest;
-    std::vector<int32_t> new_of((size_t)g->n, -1);
-    for (int32_t p = 0; p < g->n; ++p) {
-        bool in = true;
-        for (int a = 0; a < 3; ++a) { const double c = (double)rp[3 * (size_t)p + a]; in = in && c >= lo[a] && c < hi[a]; }
-        if (in) { new_of[(size_t)p] = (int32_t)w.gid.size(); w.gid.push_back(p); }
-    }
-    const size_t nw = w.gid.size();
-    w.pos.resize(3 * nw); w.vel.resize(3 * nw); w.invm.resize(nw);
-    if (!g->rest.empty()) w.rest.resize(3 * nw);
-    for (size_t k = 0; k < nw; ++k) {
-        const size_t p = (size_t)w.gid[k];
-        for (int c = 0; c < 3; ++c) {
-            w.pos[3 * k + c] = g->pos[3 * p + c]; w.vel[3 * k + c] = g->vel[3 * p + c];
-            if (!g->rest.empty()) w.rest[3 * k + c] = g->rest[3 * p + c];
-        }
-        w.invm[k] = g->invm[p];
-    }
-    const std::vector<int32_t> *I[3] = {&g->dist_ij, &g->vol_ijkl, &g->bend_ijkl};
-    const std::vector<float> *R[3] = {&g->dist_rest, &g->vol_rest, &g->bend_rest};
-    const int nv[3] = {2, 4, 4}, nr[3] = {1, 1, 2};
-    for (int t = 0; t < 3; ++t) {
-        const size_t m = R[t]->size() / (size_t)nr[t];
-        for (size_t k = 0; k < m; ++k) {
-            bool in = true;
-            for (int q = 0; q < nv[t]; ++q) in = in && new_of[(size_t)(*I[t])[nv[t] * k + q]] >= 0;
-            if (!in) continue;
-            for (int q = 0; q < nv[t]; ++q) w.idx[t].push_back(new_of[(size_t)(*I[t])[nv[t] * k + q]]);
-            for (int q = 0; q < nr[t]; ++q) w.restv[t].push_back((*R[t])[nr[t] * k + q]);
-        }
-    }
-}
-
-int author_rank(sb_group *g, int r, const sb_domain *dom) {
-    sb_solver *s = g->ranks[(size_t)r];
-    int rc;
-    if (dom) {
-        Window w;
-        cut_window(g, *dom, r, w);
-        if (w.gid.empty()) return fail(SB_ERR_INVALID_ARG, "sb_group_finalize: a rank's window of the mesh is empty (fewer occupied cells than ranks?)");
-        const int32_t nw = (int32_t)w.gid.size();
-        if ((rc = sb_set_particles(s, w.pos.data(), w.vel.data(), w.invm.data(), nw))) return rc;
-        if (!w.rest.empty() && (rc = sb_set_rest_positions(s, w.rest.data(), nw))) return rc;
-        if (!g->dist_rest.empty() && (rc = sb_set_distance_constraints(s, w.idx[0].data(), w.restv[0].data(), (int32_t)w.restv[0].size(), g->compliance[0]))) return rc;
-        if (!g->vol_rest.empty() && (rc = sb_set_volume_constraints(s, w.idx[1].data(), w.restv[1].data(), (int32_t)w.restv[1].size(), g->compliance[1]))) return rc;
-        if (!g->bend_rest.empty() && (rc = sb_set_bending_constraints(s, w.idx[2].data(), w.restv[2].data(), (int32_t)(w.restv[2].size() / 2), g->compliance[2]))) return rc;
-        if ((rc = sb_set_domain(s, dom, w.gid.data(), nw))) return rc;
-        g->gid[(size_t)r] = std::move(w.gid);
-    } else {
-        if ((rc = sb_set_particles(s, g->pos.data(), g->vel.data(), g->invm.data(), g->n))) return rc;
-        if (!g->rest.empty() && (rc = sb_set_rest_positions(s, g->rest.data(), g->n))) return rc;
-        if (!g->dist_rest.empty() && (rc = sb_set_distance_constraints(s, g->dist_ij.data(), g->dist_rest.data(), (int32_t)g->dist_rest.size(), g->compliance[0]))) return rc;
-        if (!g->vol_rest.empty() && (rc = sb_set_volume_constraints(s, g->vol_ijkl.data(), g->vol_rest.data(), (int32_t)g->vol_rest.size(), g->compliance[1]))) return rc;
-        if (!g->bend_rest.empty() && (rc = sb_set_bending_constraints(s, g->bend_ijkl.data(), g->bend_rest.data(), (int32_t)(g->bend_rest.size() / 2), g->compliance[2]))) return rc;
-    }
-    if (g->plane_set && (rc = sb_set_ground_plane(s, g->plane[0], g->plane[1], g->plane[2], g->plane[3], g->plane_on))) return rc;
+    if (sb_domain_window(dom, &o, lo, hi) != SB_OK) throw std::runtime_error(std::string("sb_group_finalize: ") + last_error_text());
+    Window w = cut_window(*g->mesh, lo, hi);
+    if (w.gid.empty()) return fail(SB_ERR_INVALID_ARG, "sb_group_finalize: a rank's window of the mesh is empty (fewer occupied cells than ranks?)");
+    s->mesh = std::make_shared<AuthoredMesh>(std::move(w.mesh));
+    s->domain = *dom;
+    s->global_id = std::move(w.gid);
+    s->sharded = true;
     return SB_OK;
 }
 
-const int32_t *id_map(const sb_group *g, int r) { return g->gid[(size_t)r].empty() ? nullptr : g->gid[(size_t)r].data(); }
+// per rank: the rank's numbering -> the caller's (sharded authoring: window index -> whole-mesh id; null = identity)
+const int32_t *id_map(const sb_group *g, int r) { const sb_solver *s = g->ranks[(size_t)r]; return s->global_id.empty() ? nullptr : s->global_id.data(); }
 
 // ---- walk mode: the calling thread takes the tick apart --------------------------------------------------------------------------------
 // One exchange step for every rank: pack kernels, then the sends and receives of ALL ranks inside one RCCL group, then the unpack
@@ -377,7 +314,8 @@ int sb_group_create(const sb_desc *desc, const int32_t *devices, int32_t n_devic
         g->desc = *desc; g->flags = flags; g->W = n_devices;
         for (int r = 0; r < n_devices; ++r) g->devices.push_back(devices ? devices[r] : r);
         g->ranks.assign((size_t)n_devices, nullptr);
-        g->gid.resize((size_t)n_devices); g->kin_ids.resize((size_t)n_devices); g->kin_pos.resize((size_t)n_devices);
+        g->mesh->group = true;
+        g->kin_ids.resize((size_t)n_devices); g->kin_pos.resize((size_t)n_devices);
         for (int r = 0; r < n_devices; ++r) {
             sb_desc d = *desc;
             d.device = g->devices[(size_t)r]; d.rank = r; d.world = n_devices;
@@ -400,59 +338,38 @@ int sb_group_destroy(sb_group *g) {
 
 int sb_group_set_particles(sb_group *g, const float *pos, const float *vel, const float *inv_mass, int32_t n) {
     if (int rc = check_group(g, false, "sb_group_set_particles")) return rc;
-    if (!pos || !inv_mass || n <= 0) return fail(SB_ERR_INVALID_ARG, "sb_group_set_particles: bad argument");
-    return guarded([&]() -> int {
-        for (int32_t p = 0; p < n; ++p) if (!(inv_mass[p] >= 0.0f)) return fail(SB_ERR_INVALID_ARG, "sb_group_set_particles: inverse mass must be >= 0");
-        g->n = n;
-        g->pos.assign(pos, pos + 3 * (size_t)n);
-        if (vel) g->vel.assign(vel, vel + 3 * (size_t)n); else g->vel.assign(3 * (size_t)n, 0.0f);
-        g->invm.assign(inv_mass, inv_mass + n);
-        return SB_OK;
-    });
+    return guarded([&]() -> int { return report(g->mesh->set_particles("sb_group_set_particles", pos, vel, inv_mass, n)); });
 }
 
 int sb_group_set_rest_positions(sb_group *g, const float *rest, int32_t n) {
     if (int rc = check_group(g, false, "sb_group_set_rest_positions")) return rc;
-    if (!rest || n != g->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_rest_positions: bad argument (n differs from sb_group_set_particles?)");
-    return guarded([&]() -> int { g->rest.assign(rest, rest + 3 * (size_t)n); return SB_OK; });
+    return guarded([&]() -> int { return report(g->mesh->set_rest_positions("sb_group_set_rest_positions", rest, n)); });
 }
 
-static int group_set_cons(sb_group *g, const char *who, const int32_t *idx, const float *rest, int32_t m, float compliance, int type, int nv, int nrest) {
+static int group_set_cons(sb_group *g, const char *who, int type, const int32_t *idx, const float *rest, int32_t m, float compliance) {
     if (int rc = check_group(g, false, who)) return rc;
-    if (m < 0 || (m > 0 && (!idx || !rest))) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": bad argument");
-    if (g->n <= 0) return fail(SB_ERR_STATE, std::string(who) + " before sb_group_set_particles");
-    if (!(compliance >= 0.0f)) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": compliance must be >= 0");
-    return guarded([&]() -> int {
-        for (int64_t k = 0; k < (int64_t)m * nv; ++k) if (idx[k] < 0 || idx[k] >= g->n) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": particle index out of range");
-        std::vector<int32_t> &I = type == 0 ? g->dist_ij : (type == 1 ? g->vol_ijkl : g->bend_ijkl);
-        std::vector<float> &R = type == 0 ? g->dist_rest : (type == 1 ? g->vol_rest : g->bend_rest);
-        I.assign(idx, idx + (size_t)m * nv);
-        R.assign(rest, rest + (size_t)m * nrest);
-        g->compliance[type] = compliance;
-        return SB_OK;
-    });
+    return guarded([&]() -> int { return report(g->mesh->set_constraints(type, who, idx, rest, m, compliance)); });
 }
 int sb_group_set_distance_constraints(sb_group *g, const int32_t *ij, const float *rest_len, int32_t m, float compliance) {
-    return group_set_cons(g, "sb_group_set_distance_constraints", ij, rest_len, m, compliance, 0, 2, 1);
+    return group_set_cons(g, "sb_group_set_distance_constraints", 0, ij, rest_len, m, compliance);
 }
 int sb_group_set_volume_constraints(sb_group *g, const int32_t *ijkl, const float *rest_vol, int32_t m, float compliance) {
-    return group_set_cons(g, "sb_group_set_volume_constraints", ijkl, rest_vol, m, compliance, 1, 4, 1);
+    return group_set_cons(g, "sb_group_set_volume_constraints", 1, ijkl, rest_vol, m, compliance);
 }
 int sb_group_set_bending_constraints(sb_group *g, const int32_t *ijkl, const float *rest_cs, int32_t m, float compliance) {
-    return group_set_cons(g, "sb_group_set_bending_constraints", ijkl, rest_cs, m, compliance, 2, 4, 2);
+    return group_set_cons(g, "sb_group_set_bending_constraints", 2, ijkl, rest_cs, m, compliance);
 }
 
 int sb_group_set_ground_plane(sb_group *g, float nx, float ny, float nz, float d, int32_t enabled) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_ground_plane: null group");
-    if (!(nx == nx) || !(ny == ny) || !(nz == nz) || !(d == d)) return fail(SB_ERR_INVALID_ARG, "sb_group_set_ground_plane: NaN");
-    g->plane[0] = nx; g->plane[1] = ny; g->plane[2] = nz; g->plane[3] = d; g->plane_on = enabled ? 1 : 0; g->plane_set = true;
+    if (int rc = report(g->mesh->set_ground_plane("sb_group_set_ground_plane", nx, ny, nz, d, enabled))) return rc;
     if (g->finalized) for (sb_solver *s : g->ranks) { const int rc = sb_set_ground_plane(s, nx, ny, nz, d, enabled); if (rc) return rc; }
     return SB_OK;
 }
 
 int sb_group_finalize(sb_group *g) {
     if (int rc = check_group(g, false, "sb_group_finalize")) return rc;
-    if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_finalize before sb_group_set_particles");
+    if (g->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_group_finalize before sb_group_set_particles");
     const int W = g->W;
     const bool peer = W > 1 && g->desc.halo_transport == SB_TRANSPORT_PEER;
     const bool no_comm = (g->desc.debug_flags & SB_DEBUG_NO_COMM) != 0;
@@ -466,18 +383,13 @@ int sb_group_finalize(sb_group *g) {
         // (SB_PARTITION_BLOCKS), or SB_PARTITION_AUTO on a LARGE mesh (the block grid is what AUTO takes for it anyway, and eight whole-mesh
         // plans of 16.8 M particles are 26 GB of host memory and 8 x 4.9 s of planning against 8 x 0.6 s on windows).
         constexpr int32_t kAutoShardParticles = 1 << 21;
-        const bool may_shard = W > 1 && !(g->flags & SB_GROUP_WHOLE_MESH) && g->desc.tile_particles >= 0 && g->vol_rest.empty() && g->bend_rest.empty() &&
-                               (g->desc.partition == SB_PARTITION_BLOCKS || (g->desc.partition == SB_PARTITION_AUTO && g->n >= kAutoShardParticles));
+        const bool may_shard = W > 1 && !(g->flags & SB_GROUP_WHOLE_MESH) && g->desc.tile_particles >= 0 && g->mesh->count(1) == 0 && g->mesh->count(2) == 0 &&
+                               (g->desc.partition == SB_PARTITION_BLOCKS || (g->desc.partition == SB_PARTITION_AUTO && g->mesh->n >= kAutoShardParticles));
         g->sharded = false;
         if (may_shard) {
-            const std::vector<float> &rp = g->rest.empty() ? g->pos : g->rest;
-            const int rc0 = sb_domain_from_mesh(rp.data(), g->n, g->dist_ij.data(), (int32_t)g->dist_rest.size(), g->vol_ijkl.data(), (int32_t)g->vol_rest.size(),
-                                                g->bend_ijkl.data(), (int32_t)(g->bend_rest.size() / 2), &dom);
-            if (rc0) return rc0;
+            dom = domain_of(make_input(*g->mesh));
             g->sharded = dom.fill >= 1.0;
         }
-        g->pinned.assign((size_t)g->n, 0);
-        for (int32_t p = 0; p < g->n; ++p) g->pinned[(size_t)p] = g->invm[(size_t)p] == 0.0f;
         if (W > 1) enable_peer_access(g);
         int rc1 = g->for_ranks([&](int r) { return guarded([&]() -> int { return author_rank(g, r, g->sharded ? &dom : nullptr); }); });
         if (rc1) return rc1;
@@ -525,7 +437,7 @@ int sb_group_finalize(sb_group *g) {
         rc1 = plan_and_compare();
         if (rc1 == SB_ERR_STATE && g->sharded) {
             g->sharded = false;
-            for (int r = 0; r < W; ++r) { reset_authoring(g->ranks[(size_t)r]); g->gid[(size_t)r].clear(); }
+            for (int r = 0; r < W; ++r) reset_authoring(g->ranks[(size_t)r]);
             if ((rc1 = g->for_ranks([&](int r) { return guarded([&]() -> int { return author_rank(g, r, nullptr); }); }))) return rc1;
             rc1 = plan_and_compare();
         }
@@ -546,23 +458,20 @@ int sb_group_finalize(sb_group *g) {
             if ((rc1 = g->for_ranks([&](int r) { return guarded([&]() -> int { int rcd = set_device(g->ranks[(size_t)r]); if (rcd) return rcd; peer_link(g->ranks[(size_t)r]); return SB_OK; }); }))) return rc1;
         }
         // ---- who owns what, in the caller's numbering ----
-        g->owner.assign((size_t)g->n, -1); g->index_in_rank.assign((size_t)g->n, -1);
+        g->owner.assign((size_t)g->mesh->n, -1); g->index_in_rank.assign((size_t)g->mesh->n, -1);
         for (int r = 0; r < W; ++r) {
             sb_solver *s = g->ranks[(size_t)r];
             const std::vector<int32_t> &own = s->plan->plan.owner_of_old;
             const int32_t *map = id_map(g, r);
-            for (int32_t o = 0; o < s->n; ++o)
+            for (int32_t o = 0; o < s->mesh->n; ++o)
                 if (own[(size_t)o] == r) {
                     const int32_t c = map ? map[o] : o;
                     if (g->owner[(size_t)c] >= 0) return fail(SB_ERR_STATE, "sb_group_finalize: internal: a particle is owned by two ranks");
                     g->owner[(size_t)c] = r; g->index_in_rank[(size_t)c] = o;
                 }
         }
-        for (int32_t c = 0; c < g->n; ++c) if (g->owner[(size_t)c] < 0) return fail(SB_ERR_STATE, "sb_group_finalize: internal: a particle is owned by no rank");
-        // the authoring copy is no longer needed
-        std::vector<float>().swap(g->pos); std::vector<float>().swap(g->vel); std::vector<float>().swap(g->invm); std::vector<float>().swap(g->rest);
-        std::vector<int32_t>().swap(g->dist_ij); std::vector<int32_t>().swap(g->vol_ijkl); std::vector<int32_t>().swap(g->bend_ijkl);
-        std::vector<float>().swap(g->dist_rest); std::vector<float>().swap(g->vol_rest); std::vector<float>().swap(g->bend_rest);
+        for (int32_t c = 0; c < g->mesh->n; ++c) if (g->owner[(size_t)c] < 0) return fail(SB_ERR_STATE, "sb_group_finalize: internal: a particle is owned by no rank");
+        g->mesh->release_bulk();       // (the ranks hold their own by now)
         g->finalized = true;
         return SB_OK;
     });
@@ -578,7 +487,7 @@ int sb_group_step(sb_group *g, float dt, int32_t substeps) {
 
 static int group_get_state(sb_group *g, float *out, int32_t n, bool velocity, const char *who) {
     if (int rc = check_group(g, true, who)) return rc;
-    if (!out || n != g->n) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": bad argument (n differs from sb_group_set_particles?)");
+    if (!out || n != g->mesh->n) return fail(SB_ERR_INVALID_ARG, std::string(who) + ": bad argument (n differs from sb_group_set_particles?)");
     if (g->W == 1) return velocity ? sb_get_velocities(g->ranks[0], out, n) : sb_get_positions(g->ranks[0], out, n);      // (the permutation runs on the GPU)
     // every rank writes the entries it owns (disjoint), the ranks side by side
     return g->for_ranks([&](int r) { return guarded([&]() -> int { return get_state_owned(g->ranks[(size_t)r], out, velocity, id_map(g, r)); }); });
@@ -588,7 +497,7 @@ int sb_group_get_velocities(sb_group *g, float *out, int32_t n) { return group_g
 
 int sb_group_set_state(sb_group *g, const float *pos, const float *vel, int32_t n) {
     if (int rc = check_group(g, true, "sb_group_set_state")) return rc;
-    if (!pos || !vel || n != g->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_state: bad argument");
+    if (!pos || !vel || n != g->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_group_set_state: bad argument");
     return g->for_ranks([&](int r) { return guarded([&]() -> int { return set_state_from(g->ranks[(size_t)r], pos, vel, id_map(g, r)); }); });
 }
 
@@ -601,8 +510,8 @@ int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const floa
         for (auto &v : g->kin_ids) v.clear();
         for (auto &v : g->kin_pos) v.clear();
         for (int32_t k = 0; k < count; ++k) {
-            if (ids[k] < 0 || ids[k] >= g->n) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle index out of range");
-            if (!g->pinned[(size_t)ids[k]])
+            if (ids[k] < 0 || ids[k] >= g->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle index out of range");
+            if (g->mesh->invm[(size_t)ids[k]] != 0.0f)
                 return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle " + std::to_string(ids[k]) + " has a non-zero inverse mass (only pinned particles are kinematic)");
             for (int c = 0; c < 3; ++c) if (!(pos[3 * (size_t)k + c] == pos[3 * (size_t)k + c])) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: NaN");
             const int r = g->owner[(size_t)ids[k]];
@@ -627,7 +536,7 @@ int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count)
     if (int rc = check_group(g, true, "sb_group_apply_impulses")) return rc;
     if (count == 0) return SB_OK;
     return guarded([&]() -> int {
-        if (int rc = validate_impulses("sb_group_apply_impulses", items, count, g->n, impulse_triangles_in_force(g->render), false)) return rc;
+        if (int rc = validate_impulses("sb_group_apply_impulses", items, count, g->mesh->n, impulse_triangles_in_force(g->render), false)) return rc;
         // SURFACE items expanded here (a triangle's particles, a vertex' cage, may belong to several ranks), then every rank its entries in
         // list order and in its own numbering; an explosion reaches the particles of every rank
         std::vector<sb_impulse> flat;
@@ -650,26 +559,26 @@ int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count)
 
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {
     if (!g || m < 0 || (m > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_triangles: bad argument");
-    if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_triangles before sb_group_set_particles");
+    if (g->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_triangles before sb_group_set_particles");
     if (g->render.pending) return fail(SB_ERR_STATE, "sb_group_set_render_triangles while a readback is pending");
     if (m > 0 && g->render.emb.m > 0)
         return fail(SB_ERR_STATE, "sb_group_set_render_triangles: a render embedding is set (switch it off first: sb_group_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
         if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        return set_render_triangles("sb_group_set_render_triangles", g->render, g->n, tri, m);
+        return set_render_triangles("sb_group_set_render_triangles", g->render, g->mesh->n, tri, m);
     });
 }
 
 int sb_group_set_render_embedding(sb_group *g, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_embedding: null group");
-    if (g->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_embedding before sb_group_set_particles");
+    if (g->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_group_set_render_embedding before sb_group_set_particles");
     if (g->render.pending) return fail(SB_ERR_STATE, "sb_group_set_render_embedding while a readback is pending");
     if (m_vertices > 0 && !g->render.tri.empty())
         return fail(SB_ERR_STATE, "sb_group_set_render_embedding: render triangles are set (switch them off first: sb_group_set_render_triangles with m = 0)");
     return guarded([&]() -> int {
         if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
         const bool was_on = g->render.emb.m > 0;
-        const int rc = set_render_embedding("sb_group_set_render_embedding", g->render, g->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri);
+        const int rc = set_render_embedding("sb_group_set_render_embedding", g->render, g->mesh->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri);
         if (rc == SB_OK && (was_on || m_vertices > 0)) for (sb_solver *s : g->ranks) if (s) s->n_peek_tiles = -1;
         return rc;
     });
@@ -679,7 +588,7 @@ int sb_group_set_render_uvs(sb_group *g, const float *uv, int32_t count) {
     if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_render_uvs: null group");
     return guarded([&]() -> int {
         if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        return set_render_uvs("sb_group_set_render_uvs", g->render, g->n, uv, count);
+        return set_render_uvs("sb_group_set_render_uvs", g->render, g->mesh->n, uv, count);
     });
 }
 
@@ -742,7 +651,7 @@ int sb_group_readback_begin(sb_group *g) {
     return guarded([&]() -> int {
         RenderState &R = g->render;
         const int W = g->W, dev0 = g->device_of(0);
-        const size_t n3 = (size_t)g->n * 3;
+        const size_t n3 = (size_t)g->mesh->n * 3;
         HIP_CHECK(hipSetDevice(dev0));
         // first use, keyed on what it creates last (the last rank's last event); every step before it can simply be done again
         if (g->rr.empty() || !g->rr.back().ev_snap[kSnapSlots - 1]) {
@@ -768,9 +677,9 @@ int sb_group_readback_begin(sb_group *g) {
         const bool compact = R.set_only && !R.tri.empty();
         if (!R.tri.empty() && R.dirty) {     // the incident-triangle lists, the render set and who owns which of its particles
             HIP_CHECK(hipStreamSynchronize(R.copy_stream));
-            const std::vector<int32_t> off = R.topo.upload(R.tri, g->n, g->dev_bytes);
+            const std::vector<int32_t> off = R.topo.upload(R.tri, g->mesh->n, g->dev_bytes);
             R.set.clear();
-            for (int32_t v = 0; v < g->n; ++v) if (off[(size_t)v + 1] > off[v]) R.set.push_back(v);
+            for (int32_t v = 0; v < g->mesh->n; ++v) if (off[(size_t)v + 1] > off[v]) R.set.push_back(v);
             R.d_set.upload(R.set, g->dev_bytes);
             upload_rank_subsets(g, R.set);
             R.dirty = false;
@@ -785,7 +694,7 @@ int sb_group_readback_begin(sb_group *g) {
             if (E.dirty) {
                 HIP_CHECK(hipStreamSynchronize(R.copy_stream));
                 std::vector<int4> cage((size_t)E.m);
-                std::vector<uint8_t> seen((size_t)g->n, 0);
+                std::vector<uint8_t> seen((size_t)g->mesh->n, 0);
                 std::vector<int32_t> distinct;
                 for (int32_t v = 0; v < E.m; ++v) {
                     const int32_t *c = &E.cage[4 * (size_t)v];
@@ -802,7 +711,7 @@ int sb_group_readback_begin(sb_group *g) {
             if (!E.tri.empty()) launch_normals_stage(R.copy_stream, R, k, E.pos[k].d.p, (int)E.m, false, (size_t)E.m, g->dev_bytes);
             launch_bounds_stage(R.copy_stream, R.bnd, k, E.pos[k].d.p, nullptr, E.m, g->dev_bytes);      // SPEC.md 6d on the skinned vertices
         } else {
-            const int count = compact ? (int)R.set.size() : (int)g->n;
+            const int count = compact ? (int)R.set.size() : (int)g->mesh->n;
             // this slot's buffers, by what it will carry (they only grow)
             if (!compact && !R.pos[k].h.p) R.pos[k].pin();
             if (!R.tri.empty()) {

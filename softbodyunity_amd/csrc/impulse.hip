@@ -198,7 +198,7 @@ int sb_apply_impulses(sb_solver *s, const sb_impulse *items, int32_t count) {
     if (count == 0) return SB_OK;
     return guarded([&]() -> int {
         const bool rank = s->desc.world > 1;
-        if (int rc = validate_impulses("sb_apply_impulses", items, count, s->n, rank ? -1 : impulse_triangles_in_force(s->render), rank)) return rc;
+        if (int rc = validate_impulses("sb_apply_impulses", items, count, s->mesh->n, rank ? -1 : impulse_triangles_in_force(s->render), rank)) return rc;
         bool surface = false;
         for (int32_t i = 0; i < count && !surface; ++i) surface = items[i].kind == SB_IMPULSE_SURFACE;
         if (!surface) return apply_impulses_validated(s, items, count);

@@ -44,9 +44,9 @@ int get_state_owned(sb_solver *s, float *out, bool velocity, const int32_t *id_m
         // single rank: every entry is ours, so the permutation to caller numbering runs on the GPU and one copy
         // lands in the caller's array (a host-side scatter costs 25 ms for 16.7 M particles)
         if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
-        if (!s->d_get_scratch.p) s->d_get_scratch.alloc((size_t)s->n * 3, s->dev_bytes);
+        if (!s->d_get_scratch.p) s->d_get_scratch.alloc((size_t)s->mesh->n * 3, s->dev_bytes);
         launch_snapshot_all(s, src, s->d_local_to_old.p, s->d_get_scratch.p);
-        HIP_CHECK(hipMemcpyAsync(out, s->d_get_scratch.p, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipMemcpyAsync(out, s->d_get_scratch.p, (size_t)s->mesh->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         return SB_OK;
     }
@@ -63,7 +63,7 @@ int get_state_owned(sb_solver *s, float *out, bool velocity, const int32_t *id_m
 static int get_state(sb_solver *s, float *out, int32_t n, bool velocity) {
     if (!s || !out) return fail(SB_ERR_INVALID_ARG, "sb_get_*: null argument");
     if (!s->finalized) return fail(SB_ERR_STATE, "sb_get_* before sb_finalize");
-    if (n != s->n) return fail(SB_ERR_INVALID_ARG, "sb_get_*: n differs from sb_set_particles");
+    if (n != s->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_get_*: n differs from sb_set_particles");
     return guarded([&]() -> int { return get_state_owned(s, out, velocity, nullptr); });
 }
 
@@ -80,7 +80,7 @@ namespace sbi {
 const std::vector<int32_t> &local_of_old(sb_solver *s) {
     if (s->local_of_old.empty()) {
         const sbp::LocalPlan &L = s->plan->local;
-        s->local_of_old.assign((size_t)s->n, -1);
+        s->local_of_old.assign((size_t)s->mesh->n, -1);
         for (size_t l = 0; l < L.local_to_old.size(); ++l) s->local_of_old[(size_t)L.local_to_old[l]] = (int32_t)l;
     }
     return s->local_of_old;
@@ -120,12 +120,12 @@ int set_state_from(sb_solver *s, const float *pos, const float *vel, const int32
 int set_kinematic(sb_solver *s, const int32_t *ids, const float *pos, int32_t count) {
     int rc = set_device(s); if (rc) return rc;
     const std::vector<int32_t> &lof = local_of_old(s);
-    if (s->kin_seen.size() != (size_t)s->n) s->kin_seen.assign((size_t)s->n, 0);
+    if (s->kin_seen.size() != (size_t)s->mesh->n) s->kin_seen.assign((size_t)s->mesh->n, 0);
     const uint32_t stamp = ++s->kin_stamp;
     int32_t n_mine = 0;
     for (int32_t k = 0; k < count; ++k) {
-        if (ids[k] < 0 || ids[k] >= s->n) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle index out of range");
-        if (s->invm[(size_t)ids[k]] != 0.0f)
+        if (ids[k] < 0 || ids[k] >= s->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle index out of range");
+        if (s->mesh->invm[(size_t)ids[k]] != 0.0f)
             return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: particle " + std::to_string(ids[k]) + " has a non-zero inverse mass (only pinned particles are kinematic)");
         for (int c = 0; c < 3; ++c) if (!(pos[3 * (size_t)k + c] == pos[3 * (size_t)k + c])) return fail(SB_ERR_INVALID_ARG, "sb_set_kinematic_positions: NaN");
         // each id at most once: twice would be an order-dependent result and, in the fused path, a write race on one target slot
@@ -161,7 +161,7 @@ extern "C" {
 int sb_set_state(sb_solver *s, const float *pos, const float *vel, int32_t n) {
     if (!s || !pos || !vel) return fail(SB_ERR_INVALID_ARG, "sb_set_state: null argument");
     if (!s->finalized) return fail(SB_ERR_STATE, "sb_set_state before sb_finalize");
-    if (n != s->n) return fail(SB_ERR_INVALID_ARG, "sb_set_state: n differs from sb_set_particles");
+    if (n != s->mesh->n) return fail(SB_ERR_INVALID_ARG, "sb_set_state: n differs from sb_set_particles");
     return guarded([&]() -> int { return set_state_from(s, pos, vel, nullptr); });
 }
 

@@ -358,7 +358,7 @@ int sb_readback_begin(sb_solver *s) {
         }
         const int k = R.next_slot();
         if (R.emb.m > 0) { begin_embedded(s, k); return SB_OK; }       // (no particle snapshot: its n-sized buffers are not even allocated)
-        const size_t n3 = (size_t)s->n * 3;
+        const size_t n3 = (size_t)s->mesh->n * 3;
         if (!R.pos[kSnapSlots - 1].h.p) {      // first use: a slot counts as made once its pinned side is there, which comes last
             if (!s->d_local_to_old.p) s->d_local_to_old.upload(s->plan->local.local_to_old, s->dev_bytes);
             for (int q = 0; q < kSnapSlots; ++q) {
@@ -376,10 +376,10 @@ int sb_readback_begin(sb_solver *s) {
         const bool single = s->desc.world == 1;
         if (!R.tri.empty() && R.dirty) {     // the incident-triangle lists, and the render set: the particles they name that this rank owns
             HIP_CHECK(hipStreamSynchronize(R.copy_stream));
-            const std::vector<int32_t> off = R.topo.upload(R.tri, s->n, s->dev_bytes);
+            const std::vector<int32_t> off = R.topo.upload(R.tri, s->mesh->n, s->dev_bytes);
             const std::vector<int32_t> &lof = local_of_old(s);
             R.set.clear(); s->render_local.clear();
-            for (int32_t v = 0; v < s->n; ++v)
+            for (int32_t v = 0; v < s->mesh->n; ++v)
                 if (off[(size_t)v + 1] > off[v] && lof[(size_t)v] >= 0 && lof[(size_t)v] < s->n_owned) { R.set.push_back(v); s->render_local.push_back(lof[(size_t)v]); }
             R.d_set.upload(R.set, s->dev_bytes);
             s->d_render_local.upload(s->render_local, s->dev_bytes);
@@ -411,10 +411,10 @@ int sb_readback_begin(sb_solver *s) {
         R.slot[k].has_render_set = !R.tri.empty();
         R.tan.snap_has[k] = false;
         if (compact && !single) R.cpos[k].copy_out(R.copy_stream, (size_t)cnt * 3);
-        if (!R.tri.empty() && single) launch_normals_stage(R.copy_stream, R, k, R.pos[k].d.p, compact ? cnt : (int)s->n, compact, (size_t)s->n, s->dev_bytes);
+        if (!R.tri.empty() && single) launch_normals_stage(R.copy_stream, R, k, R.pos[k].d.p, compact ? cnt : (int)s->mesh->n, compact, (size_t)s->mesh->n, s->dev_bytes);
         // SPEC.md 6d on what this snapshot delivers: the compact array, or the rows of the full one this rank owns
         if (compact) launch_bounds_stage(R.copy_stream, R.bnd, k, R.cpos[k].d.p, nullptr, cnt, s->dev_bytes);
-        else launch_bounds_stage(R.copy_stream, R.bnd, k, R.pos[k].d.p, single ? (const int32_t *)nullptr : s->d_local_to_old.p, single ? (int64_t)s->n : s->n_owned, s->dev_bytes);
+        else launch_bounds_stage(R.copy_stream, R.bnd, k, R.pos[k].d.p, single ? (const int32_t *)nullptr : s->d_local_to_old.p, single ? (int64_t)s->mesh->n : s->n_owned, s->dev_bytes);
         HIP_CHECK(hipEventRecord(R.ev_copied[k], R.copy_stream));
         ++R.pending;
         return SB_OK;
@@ -435,11 +435,11 @@ int sb_readback_end(sb_solver *s, const float **pos_xyz_out) {
 
 int sb_set_render_triangles(sb_solver *s, const int32_t *tri, int32_t m) {
     if (!s || m < 0 || (m > 0 && !tri)) return fail(SB_ERR_INVALID_ARG, "sb_set_render_triangles: bad argument");
-    if (s->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_triangles before sb_set_particles");
+    if (s->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_triangles before sb_set_particles");
     if (s->render.pending) return fail(SB_ERR_STATE, "sb_set_render_triangles while a readback is pending");
     if (m > 0 && s->render.emb.m > 0)
         return fail(SB_ERR_STATE, "sb_set_render_triangles: a render embedding is set (switch it off first: sb_set_render_embedding with m_vertices = 0)");
-    return guarded([&]() -> int { return set_render_triangles("sb_set_render_triangles", s->render, s->n, tri, m); });
+    return guarded([&]() -> int { return set_render_triangles("sb_set_render_triangles", s->render, s->mesh->n, tri, m); });
 }
 
 int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float *weights4, int32_t m_vertices, const int32_t *tri_abc, int32_t m_tri) {
@@ -447,14 +447,14 @@ int sb_set_render_embedding(sb_solver *s, const int32_t *cage_ijkl, const float 
     if (s->desc.world > 1)
         return fail(SB_ERR_UNSUPPORTED, "sb_set_render_embedding: a rank of a partitioned solver does not hold every cage particle; a partitioned body is "
                     "skinned on the gathered snapshot (sb_group_set_render_embedding)");
-    if (s->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_embedding before sb_set_particles");
+    if (s->mesh->n <= 0) return fail(SB_ERR_STATE, "sb_set_render_embedding before sb_set_particles");
     if (s->render.pending) return fail(SB_ERR_STATE, "sb_set_render_embedding while a readback is pending");
     if (m_vertices > 0 && !s->render.tri.empty())
         return fail(SB_ERR_STATE, "sb_set_render_embedding: render triangles are set (switch them off first: sb_set_render_triangles with m = 0)");
     return guarded([&]() -> int {
         if (s->finalized) { int rc = set_device(s); if (rc) return rc; }
         const bool was_on = s->render.emb.m > 0;
-        const int rc = set_render_embedding("sb_set_render_embedding", s->render, s->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri);
+        const int rc = set_render_embedding("sb_set_render_embedding", s->render, s->mesh->n, cage_ijkl, weights4, m_vertices, tri_abc, m_tri);
         if (rc == SB_OK && (was_on || m_vertices > 0)) s->n_peek_tiles = -1;
         return rc;
     });
@@ -475,7 +475,7 @@ int sb_set_render_uvs(sb_solver *s, const float *uv, int32_t count) {
                     "body are computed on the gathered snapshot (sb_group_set_render_uvs)");
     return guarded([&]() -> int {
         if (s->finalized) { int rc = set_device(s); if (rc) return rc; }
-        return set_render_uvs("sb_set_render_uvs", s->render, s->n, uv, count);
+        return set_render_uvs("sb_set_render_uvs", s->render, s->mesh->n, uv, count);
     });
 }
 

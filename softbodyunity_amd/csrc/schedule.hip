@@ -22,12 +22,12 @@ sbk::TickParams tick_params(const sb_solver *s, float dt, int substeps) {
     volatile float kd = 1.0f - td;
     t.kd = kd < 0.0f ? 0.0f : (float)kd;
     volatile float h2 = h * h;
-    volatile float ad = s->compliance[0] / h2;
-    volatile float av = s->compliance[1] / h2;
+    volatile float ad = s->mesh->kind[0].compliance / h2;
+    volatile float av = s->mesh->kind[1].compliance / h2;
     volatile float av36 = 36.0f * av;
-    volatile float ab = s->compliance[2] / h2;
+    volatile float ab = s->mesh->kind[2].compliance / h2;
     t.at_d = ad; t.at_v = av36; t.at_b = ab;
-    t.pnx = s->plane[0]; t.pny = s->plane[1]; t.pnz = s->plane[2]; t.pd = s->plane[3]; t.plane_on = s->plane_on;
+    t.pnx = s->mesh->plane[0]; t.pny = s->mesh->plane[1]; t.pnz = s->mesh->plane[2]; t.pd = s->mesh->plane[3]; t.plane_on = s->mesh->plane_on;
     return t;
 }
 
@@ -454,7 +454,7 @@ void stage_kinematic_for_fusion(sb_solver *s) {
         const sbp::LocalPlan &L = s->plan->local;
         std::vector<int32_t> map((size_t)s->n_local, -1);
         int32_t n_pinned = 0;
-        for (int64_t l = 0; l < s->n_local; ++l) if (s->invm[(size_t)L.local_to_old[(size_t)l]] == 0.0f) map[(size_t)l] = n_pinned++;
+        for (int64_t l = 0; l < s->n_local; ++l) if (s->mesh->invm[(size_t)L.local_to_old[(size_t)l]] == 0.0f) map[(size_t)l] = n_pinned++;
         std::vector<float> nan((size_t)std::max(n_pinned, 1) * 3, std::numeric_limits<float>::quiet_NaN());
         s->d_kin_target.upload(nan, s->dev_bytes);
         s->d_kin_map.upload(map, s->dev_bytes);

@@ -4,7 +4,8 @@
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
 // tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
-// and a group share -- render.hpp -- and the solver's entry points), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
+// and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
+// window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,10 +38,12 @@
 #include "kernel_types.hpp"
 #include "plan.hpp"
 #include "tables_host.hpp"
+#include "authoring.hpp"
 
 namespace sbi {
 
 int fail(int code, const std::string &msg);      // records the thread's last error (sb_last_error) and returns code
+inline int report(const Status &st) { return st.code == SB_OK ? (int)SB_OK : fail(st.code, st.text); }      // what authoring.cpp answered
 const char *last_error_text();
 
 struct HipError : std::runtime_error {
@@ -163,17 +166,12 @@ struct sb_solver {
     sbi::Stream comm_stream;
     sbi::Event ev_boundary, ev_halo;
     bool overlap_halo = false;       // T0 boundary tiles first, ghost exchange on comm_stream beside the interior
-    // authoring copies
-    int32_t n = 0;
-    std::vector<float> pos, vel, invm, rest;
-    bool sharded = false;            // sb_set_domain: the authoring arrays are this rank's window of a larger mesh
+    // What was authored (authoring.hpp): the solver's own, its window of a group's mesh, or -- only read, until finalize_link leaves this
+    // rank a copy of what it needs afterwards -- the whole mesh the ranks of a group share with the group
+    std::shared_ptr<sbi::AuthoredMesh> mesh = std::make_shared<sbi::AuthoredMesh>();
+    bool sharded = false;            // sb_set_domain: the mesh is this rank's window of a larger one
     sb_domain domain{};
     std::vector<int32_t> global_id;  // [n] ids of the window's particles in the whole mesh (sharded only)
-    std::vector<int32_t> dist_ij, vol_ijkl, bend_ijkl;
-    std::vector<float> dist_rest, vol_rest, bend_rest;
-    float compliance[3] = {0, 0, 0};
-    float plane[4] = {0, 1, 0, 0};
-    int32_t plane_on = 0;
     // plan
     std::unique_ptr<sb_plan> plan;
     // device state
@@ -321,6 +319,7 @@ namespace sbi {
 // ---- tables.hip: plan -> device tables (built by tables_host.cpp) ---------------------------------------------------------------------------------------------
 sbp::Input make_input(const float *rest, int32_t n, const int32_t *d, int64_t md, const int32_t *v, int64_t mv, const int32_t *b, int64_t mb);
 sbp::Domain to_domain(const sb_domain &d);
+sb_domain domain_of(const sbp::Input &in);       // abi.hip: what sb_domain_from_mesh measures
 // The planner options behind the ABI's fields: ONE rule for sb_finalize and sb_plan_build
 sbp::Opts plan_opts(int rank, int world, const int32_t dims[3], int32_t tile_particles, int32_t partition, uint32_t plan_flags,
                     int64_t m_v, int64_t m_b, const sb_domain *domain = nullptr);

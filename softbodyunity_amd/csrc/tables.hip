@@ -104,8 +104,9 @@ static void alloc_mailbox(sb_solver *s, sbt::HostMailbox &M) {
 // placement experiments (sb_tuning.prev_offset_bytes) depend on what is allocated before what.
 void build_device(sb_solver *s) {
     const sbp::LocalPlan &L = s->plan->local;
-    const sbt::TableInput in{&s->plan->plan, &L, s->pos.data(), s->vel.data(), s->invm.data(), s->dist_rest.data(), s->vol_rest.data(),
-                             s->bend_rest.data(), (int64_t)s->vol_rest.size(), (int64_t)s->bend_rest.size()};
+    const AuthoredMesh &M = *s->mesh;
+    const sbt::TableInput in{&s->plan->plan, &L, M.pos.data(), M.vel.data(), M.invm.data(), M.kind[0].rest.data(), M.kind[1].rest.data(),
+                             M.kind[2].rest.data(), (int64_t)M.kind[1].rest.size(), (int64_t)M.kind[2].rest.size()};
     sbt::TableOptions opt;
     opt.tune_flags = s->tune_flags; opt.tile_lanes = s->tile_lanes; opt.quad_lanes = s->quad_lanes; opt.narrow_min_tiles = s->narrow_min_tiles;
     opt.pack_tiles = s->pack_tiles; opt.win_dwords_cap = s->win_dwords_cap;

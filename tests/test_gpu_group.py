@@ -100,3 +100,45 @@ def test_group_calls_out_of_order_are_refused():
         assert L.sb_group_readback_begin(g) == native.SB_ERR_STATE                                  # two pending already
     finally:
         assert L.sb_group_destroy(g) == native.SB_OK                                                # with snapshots still pending
+
+
+def test_windows_that_are_refused_leave_every_rank_the_whole_mesh():
+    """The fall-back of sb_group_finalize: a mesh that may be sharded (distance constraints only, fill 1, block partition) whose windows do
+    not reproduce the whole-mesh plan -- 12 particles on a line, nearest-neighbour springs, four ranks: one window plans a leftover layer
+    the others lack (found on the CPU with tests/fuzz/fuzz_windows.py's run: REFUSED, halo slots [3, 3, 3, 4]). The ranks' agreement check
+    refuses the windows and every rank is handed the group's mesh instead. No tick: there is no transport (SB_DEBUG_NO_COMM)."""
+    import ctypes as C
+    import numpy as np
+    from softbodyunity_amd import SoftbodyGroup, native
+    from softbodyunity_amd.mesh import SoftbodyMesh
+    n, W, tile = 12, 4, 4
+    rng = np.random.default_rng(0)
+    x = np.cumsum(rng.uniform(0.5, 1.5, n)).astype(np.float32)
+    rest = np.stack([x, np.zeros(n, np.float32), np.zeros(n, np.float32)], 1)
+    ij = np.stack([np.arange(n - 1), np.arange(1, n)], 1).astype(np.int32)
+    pos = (rest + rng.uniform(-0.1, 0.1, rest.shape)).astype(np.float32)
+    mesh = SoftbodyMesh(rest_pos=rest, pos=pos, vel=np.zeros_like(pos), inv_mass=np.ones(n, np.float32), dist_ij=ij, dist_rest=(x[1:] - x[:-1]).astype(np.float32))
+    # what the group is about to find, on the host-only planner: every window a proper part of the mesh, their tick programs of different shape
+    dom = native.domain_from_mesh(rest, ij)
+    assert dom.fill >= 1.0
+    slots = []
+    for r in range(W):
+        lo, hi = native.domain_window(dom, r, W, (0, 0, 0), tile)
+        gid = np.nonzero(np.all((rest >= lo) & (rest < hi), axis=1))[0].astype(np.int32)
+        assert 0 < len(gid) < n
+        new = -np.ones(n, np.int64); new[gid] = np.arange(len(gid))
+        wij = new[ij[np.all(new[ij] >= 0, axis=1)]].astype(np.int32)
+        slots.append(native.Plan.build(rest[gid], wij, rank=r, world=W, tile_particles=tile, partition=native.SB_PARTITION_BLOCKS, domain=dom, global_id=gid).halo_slot_count())
+    assert len(set(slots)) > 1, slots
+    g = SoftbodyGroup(mesh, [0] * W, substeps=4, tile_particles=tile, partition=native.SB_PARTITION_BLOCKS, debug_flags=native.SB_DEBUG_NO_COMM).Start()
+    try:
+        L = native.lib()
+        owners = []
+        for r in range(W):
+            own = np.full(n, -1, np.int32)
+            native.check(L.sb_get_owner(g._rank_handle(r), native.ptr(own), n))      # (a rank that kept its window holds fewer than n)
+            owners.append(own)
+        assert all(np.array_equal(o, owners[0]) for o in owners) and set(owners[0].tolist()) <= set(range(W))
+        assert np.array_equal(g.get_positions().view(np.uint32), pos.view(np.uint32))
+    finally:
+        g.OnDestroy()
