@@ -1,7 +1,8 @@
-// device_handles.hpp — the owners of what the HIP runtime hands out: events, streams, device memory, pinned host memory, and the ring of
-// mapped pinned tables the kinematic targets and the impulses travel in. Plain move-only types whose destructor gives the resource back;
-// included by solver_internal.hpp (after HIP_CHECK). No other file of the plugin creates or destroys one of these resources by hand
-// (the peer mailbox, which has two ways to be allocated and mappings in other processes, is PeerState's own business).
+// device_handles.hpp — the owners of what the HIP runtime hands out: events, streams, device memory, pinned host memory, the ring of
+// mapped pinned tables the kinematic targets and the impulses travel in, and the cache of sb_step's graph executables. Plain types,
+// move-only or fixed in place, whose destructor gives the resource back; included by solver_internal.hpp (after HIP_CHECK).
+// No other file of the plugin creates or destroys one of these resources by hand (the peer mailbox, which has two ways to be
+// allocated and mappings in other processes, is PeerState's own business).
 //
 // FIRST USE. Much of the solver's device state is made at the first call that needs it, inside `if (!x) { ... }`. Such a block is ALL OR
 // NOTHING: either it is keyed on the thing it creates LAST (every step before it may then simply be done again: create() is idempotent,
@@ -123,6 +124,42 @@ struct TableRing {
     char *host(int q) { return table[q].p; }
     const char *device(int q) const { return table[q].dev; }
     void retire(int q, hipStream_t st) { HIP_CHECK(hipEventRecord(done[q], st)); }
+};
+
+// The instantiated graphs of sb_step, one per key (a tick flavour): at most kMaxGraphs are kept, the least recently used one goes when
+// another arrives (a host that varies substeps). The executables are destroyed with the cache, or earlier by clear().
+struct GraphCache {
+    static constexpr size_t kMaxGraphs = 8;
+    struct Entry { hipGraphExec_t exec; uint64_t last_use; };
+    std::map<int, Entry> entries;
+    uint64_t clock = 0;
+    GraphCache() = default;
+    GraphCache(const GraphCache &) = delete;
+    GraphCache &operator=(const GraphCache &) = delete;
+    hipGraphExec_t find(int key) {               // null: not instantiated yet (or evicted since)
+        auto it = entries.find(key);
+        if (it == entries.end()) return nullptr;
+        it->second.last_use = ++clock;
+        return it->second.exec;
+    }
+    // Instantiates the captured graph `g` under `key` and destroys g; `st` is the stream an evicted executable may still be running on.
+    hipGraphExec_t add(int key, hipGraph_t g, hipStream_t st) {
+        hipGraphExec_t ge = nullptr;
+        hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (e != hipSuccess) throw HipError(SB_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+        if (entries.size() >= kMaxGraphs) {
+            auto old = entries.begin();
+            for (auto q = entries.begin(); q != entries.end(); ++q) if (q->second.last_use < old->second.last_use) old = q;
+            HIP_CHECK(hipStreamSynchronize(st));
+            (void)hipGraphExecDestroy(old->second.exec);
+            entries.erase(old);
+        }
+        entries.emplace(key, Entry{ge, ++clock});
+        return ge;
+    }
+    void clear() { for (auto &g : entries) (void)hipGraphExecDestroy(g.second.exec); entries.clear(); }
+    ~GraphCache() { clear(); }
 };
 
 }  // namespace sbi

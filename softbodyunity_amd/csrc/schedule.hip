@@ -3,6 +3,7 @@
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
 #include "solver_internal.hpp"
+#include "launch_shape.hpp"
 #include "tile_kernel.hip.hpp"
 #include "aux_kernels.hip.hpp"
 
@@ -40,7 +41,7 @@ void peer_link(sb_solver *s) {
         const DevHalo &D = *s->halos[(size_t)slot];
         sbk::PeerSlot &P = PS.slots[(size_t)slot];
         const size_t base = PS.slot_base(slot, W);
-        const size_t fl = slot == 1 ? 6 : 3;
+        const size_t fl = sbt::ghost_floats((size_t)slot);
         P.local = PS.local.p + (size_t)slot * 8;
         P.error = PS.h_error.p;       // (pinned host memory is device-accessible at the same address)
         for (size_t k = 0; k < D.peers.size(); ++k) {
@@ -113,46 +114,47 @@ void peer_link(sb_solver *s) {
 //   halo_exchange_post   RCCL: the unpack kernel (none behind a fused exchange)
 bool halo_slot_active(const sb_solver *s, int slot) { return slot >= 0 && slot < (int)s->halos.size() && s->halos[(size_t)slot]->active(); }
 
+// The pack / unpack kernels between the state and the send / receive buffer of one halo slot (slot 1 also carries previous positions).
+static void launch_halo_pack(sb_solver *s, const DevHalo &D, int slot, hipStream_t st) {
+    const int ns = D.send_off.back();
+    if (!ns) return;
+    auto *pack = slot == 1 ? sbk::halo_pack_kernel<true> : sbk::halo_pack_kernel<false>;
+    hipLaunchKernelGGL(pack, dim3((ns + 255) / 256), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.send_idx.p, s->d_sendbuf.p, ns);
+}
+static void launch_halo_unpack(sb_solver *s, const DevHalo &D, int slot, hipStream_t st) {
+    const int nr = D.recv_off.back();
+    if (!nr || (slot == 1 && s->fused_unpack)) return;      // (fused: the T1 kernels read the ghosts from the receive buffer, nothing to scatter)
+    auto *unpack = slot == 1 ? sbk::halo_unpack_kernel<true> : sbk::halo_unpack_kernel<false>;
+    hipLaunchKernelGGL(unpack, dim3((nr + 255) / 256), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.recv_idx.p, s->d_recvbuf.p, nr);
+}
+
 void halo_exchange_pre(sb_solver *s, int slot, hipStream_t st) {
     if (!halo_slot_active(s, slot)) return;
     DevHalo &D = *s->halos[slot];
-    const bool with_prev = slot == 1;
-    const int ns = D.send_off.back(), nr = D.recv_off.back();
     if (s->peer.enabled) {
         if (!s->peer.linked) peer_link(s);
         const sbk::PeerSlot &P = s->peer.slots[(size_t)slot];
-        const int push_chunks = ns, unpack_chunks = nr;       // one lane per ghost (send_idx / recv_idx are indexed by the absolute position)
-        // two launches per exchange, both always (the push also carries the waits, the unpack advances the slot's epoch);
-        // at most kPeerGrid workgroups each: they end with an atomic on one word
+        // two launches per exchange, both always (the push also carries the waits, the unpack advances the slot's epoch), one lane per
+        // ghost (send_idx / recv_idx are indexed by the absolute position); at most kPeerGrid workgroups each: they end with an atomic on one word
         constexpr int kPeerGrid = 128;
-        if (with_prev) {
-            hipLaunchKernelGGL(sbk::peer_push_kernel<true>, dim3(std::min(kPeerGrid, std::max(1, (push_chunks + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.send_idx.p, push_chunks, P);
-            hipLaunchKernelGGL(sbk::peer_unpack_kernel<true>, dim3(std::min(kPeerGrid, std::max(1, (unpack_chunks + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.recv_idx.p, unpack_chunks, P);
-        } else {
-            hipLaunchKernelGGL(sbk::peer_push_kernel<false>, dim3(std::min(kPeerGrid, std::max(1, (push_chunks + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.send_idx.p, push_chunks, P);
-            hipLaunchKernelGGL(sbk::peer_unpack_kernel<false>, dim3(std::min(kPeerGrid, std::max(1, (unpack_chunks + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.recv_idx.p, unpack_chunks, P);
-        }
+        const int ns = D.send_off.back(), nr = D.recv_off.back();
+        auto *push = slot == 1 ? sbk::peer_push_kernel<true> : sbk::peer_push_kernel<false>;
+        auto *unpack = slot == 1 ? sbk::peer_unpack_kernel<true> : sbk::peer_unpack_kernel<false>;
+        hipLaunchKernelGGL(push, dim3(std::min(kPeerGrid, std::max(1, (ns + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.send_idx.p, ns, P);
+        hipLaunchKernelGGL(unpack, dim3(std::min(kPeerGrid, std::max(1, (nr + 255) / 256))), dim3(256), 0, st, s->pos_view(), s->d_prev.p, D.recv_idx.p, nr, P);
         return;
     }
     if (!s->comm) throw HipError(SB_ERR_STATE, "world > 1 needs sb_comm_init before sb_finalize");
-    if (ns) {
-        if (with_prev)
-            hipLaunchKernelGGL(sbk::halo_pack_kernel<true>, dim3((ns + 255) / 256), dim3(256), 0, st, s->pos_view(),
-                               s->d_prev.p, D.send_idx.p, s->d_sendbuf.p, ns);
-        else
-            hipLaunchKernelGGL(sbk::halo_pack_kernel<false>, dim3((ns + 255) / 256), dim3(256), 0, st, s->pos_view(),
-                               s->d_prev.p, D.send_idx.p, s->d_sendbuf.p, ns);
-    }
+    launch_halo_pack(s, D, slot, st);
 }
 
 void halo_exchange_calls(sb_solver *s, int slot, hipStream_t st) {
     if (!halo_slot_active(s, slot) || s->peer.enabled) return;
     DevHalo &D = *s->halos[slot];
-    const bool with_prev = slot == 1;
+    const size_t fl = sbt::ghost_floats((size_t)slot);   // floats per ghost; one message per peer and direction
     for (size_t k = 0; k < D.peers.size(); ++k) {
         int cs = D.send_off[k + 1] - D.send_off[k], cr = D.recv_off[k + 1] - D.recv_off[k];
         if (s->loopback) cs = cr = std::min(cs, cr);   // a self-exchange must post equal sizes (real peers always do)
-        const size_t fl = with_prev ? 6 : 3;   // floats per ghost; one message per peer and direction
         if (cs) NCCL_CHECK(rccl().Send(s->d_sendbuf.p + fl * D.send_off[k], fl * (size_t)cs, ncclFloat, s->loopback ? 0 : D.peers[k], s->comm, st));
         if (cr) NCCL_CHECK(rccl().Recv(s->d_recvbuf.p + fl * D.recv_off[k], fl * (size_t)cr, ncclFloat, s->loopback ? 0 : D.peers[k], s->comm, st));
     }
@@ -160,17 +162,7 @@ void halo_exchange_calls(sb_solver *s, int slot, hipStream_t st) {
 
 void halo_exchange_post(sb_solver *s, int slot, hipStream_t st) {
     if (!halo_slot_active(s, slot) || s->peer.enabled) return;
-    DevHalo &D = *s->halos[slot];
-    const bool with_prev = slot == 1;
-    const int nr = D.recv_off.back();
-    if (nr && !(with_prev && s->fused_unpack)) {
-        if (with_prev)
-            hipLaunchKernelGGL(sbk::halo_unpack_kernel<true>, dim3((nr + 255) / 256), dim3(256), 0, st, s->pos_view(),
-                               s->d_prev.p, D.recv_idx.p, s->d_recvbuf.p, nr);
-        else
-            hipLaunchKernelGGL(sbk::halo_unpack_kernel<false>, dim3((nr + 255) / 256), dim3(256), 0, st, s->pos_view(),
-                               s->d_prev.p, D.recv_idx.p, s->d_recvbuf.p, nr);
-    }
+    launch_halo_unpack(s, *s->halos[slot], slot, st);
 }
 
 // Exchange timing (sb_debug_exchange_timing): three events per exchange on the stream it runs on -- start, after the pack (or push)
@@ -212,6 +204,23 @@ void halo_exchange(sb_solver *s, int slot, hipStream_t st) {
     if (timed) s->xtimer.mark(st);
 }
 
+// The one place that launches tile_kernel: the block size IS the kernel's THREADS.
+template <int KIND, bool Q, int THREADS, int PPT, bool W, int G>
+void launch_tile_kernel(const sb_solver *s, const DevTiling &D, const sbk::TileDesc *tiles_at_base, int n_wg, const sbk::TileArgs &A) {
+    hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, THREADS, PPT, W, G>), dim3(n_wg), dim3(THREADS), D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);
+}
+// From the shape (launch_shape.hpp) to the instantiation. 512 x 2 is built for tiles with tets / hinges only; a shape without a kernel is an error.
+template <int KIND, bool Q, bool W, int G>
+void launch_tile_shaped(const sb_solver *s, const DevTiling &D, const sbt::LaunchShape &sh, const sbk::TileDesc *tiles_at_base, int n_wg, const sbk::TileArgs &A) {
+    using namespace sbt;
+    if (same_width(sh, kShapeEight)) return launch_tile_kernel<KIND, Q, kShapeEight.threads, kShapeEight.ppt, W, G>(s, D, tiles_at_base, n_wg, A);
+    if constexpr (Q) if (same_width(sh, kShapeEightLarge)) return launch_tile_kernel<KIND, Q, kShapeEightLarge.threads, kShapeEightLarge.ppt, W, G>(s, D, tiles_at_base, n_wg, A);
+    if (same_width(sh, kShapeNarrow)) return launch_tile_kernel<KIND, Q, kShapeNarrow.threads, kShapeNarrow.ppt, W, G>(s, D, tiles_at_base, n_wg, A);
+    if (same_width(sh, kShapeWide)) return launch_tile_kernel<KIND, Q, kShapeWide.threads, kShapeWide.ppt, W, G>(s, D, tiles_at_base, n_wg, A);
+    if (same_width(sh, kShapeWideLarge)) return launch_tile_kernel<KIND, Q, kShapeWideLarge.threads, kShapeWideLarge.ppt, W, G>(s, D, tiles_at_base, n_wg, A);
+    throw std::runtime_error("internal: no tile kernel is built for the launch shape asked for");
+}
+
 // `table` (KIND 4 only): a descriptor table of its own -- copies of some of D's descriptors -- instead of D's tiles [tile_begin, tile_end)
 template <int KIND>
 void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = -1, int halo = sbk::kHaloNone, const sbk::TileDesc *table = nullptr) {
@@ -232,45 +241,16 @@ void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = 
     A.max_local = D.max_local; A.win_dwords = D.win_dwords; A.tile_base = tile_begin; A.pal_dwords = D.pal_dwords; A.rounds_dwords = D.rounds_dwords;
     const sbk::TileDesc *tiles_at_base = table ? table : D.tiles.p + tile_begin;      // the two preloaded kernel arguments (tile_kernel)
     const int n_wg = tile_end - tile_begin;
-    const bool small = D.max_local <= sbk::kSmallTile;   // every tile <= 512 particles
-    // narrow (2-wave) workgroups once the launch oversubscribes the chip; wide ones while every tile is resident at once
-    // (a tiling with lane-packed slots runs 128-lane workgroups in EVERY launch, also the peek's subset of its tiles)
-    // (a tiling with 8-byte wide-packed slots likewise runs 256-lane workgroups in every launch)
-    const bool narrow = small && (D.packed_lanes ? D.packed_lanes == sbk::kLanePackLanes : (s->tile_lanes ? s->tile_lanes == sbk::kNarrowTileThreads : tile_end - tile_begin >= s->narrow_min_tiles));
-    // tiles with tets / hinges: optionally 8 waves, so that a group's wave slots (16 four-lane constraints or 64 springs each) fit one row
-    const bool quad8 = D.has_quads && s->quad_lanes == sbk::kQuadTileThreads;
-    // spring-only small tiles on 8 waves (one particle per lane in the load / MARK / store phases; the rounds use half the lanes) while
-    // every workgroup of the launch is resident even at that width (4 per compute unit): 64^3 0.1244 -> 0.1213, 48^3 0.1027 -> 0.1005 ms
-    // per tick; 96^3 (1 728 tiles) 0.206 -> 0.230, so only launches of at most kWide8MaxTiles (profiles/r03o_lanes512_small_cubes.txt)
-    constexpr int kWide8MaxTiles = sbk::kWide8MaxTiles;
-    const bool wide8 = small && !D.has_quads && !D.packed_lanes && (s->tile_lanes ? s->tile_lanes == 512 : tile_end - tile_begin <= kWide8MaxTiles);
-    const dim3 grid(tile_end - tile_begin), block(quad8 || wide8 ? sbk::kQuadTileThreads : (narrow ? sbk::kNarrowTileThreads : sbk::kWideTileThreads));
-#define SB_LAUNCH_TILE(Q, W, G)                                                                                               \
-    do {                                                                                                                      \
-        if (Q && quad8) {                                                                                                     \
-            if (small) hipLaunchKernelGGL((sbk::tile_kernel<KIND, true, sbk::kQuadTileThreads, sbk::kSmallTile / sbk::kQuadTileThreads, W, sbk::kHaloNone>), \
-                                          grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                           \
-            else hipLaunchKernelGGL((sbk::tile_kernel<KIND, true, sbk::kQuadTileThreads, sbk::kLargeTile / sbk::kQuadTileThreads, W, sbk::kHaloNone>), \
-                                    grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                                 \
-        } else if (wide8) hipLaunchKernelGGL((sbk::tile_kernel<KIND, false, sbk::kQuadTileThreads, sbk::kSmallTile / sbk::kQuadTileThreads, W, G>), \
-                                       grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                              \
-        else if (narrow) hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, sbk::kNarrowTileThreads, sbk::kSmallTile / sbk::kNarrowTileThreads, W, G>), \
-                                       grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                              \
-        else if (small) hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, sbk::kWideTileThreads, sbk::kSmallTile / sbk::kWideTileThreads, W, G>), \
-                                           grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                          \
-        else hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, sbk::kWideTileThreads, sbk::kLargeTile / sbk::kWideTileThreads, W, G>), \
-                                grid, block, D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);                                                     \
-    } while (0)
+    const sbt::LaunchShape sh = sbt::tile_launch_shape(D, s->tile_lanes, s->quad_lanes, s->narrow_min_tiles, n_wg, ghosts);
     // the ghost-reading variant exists for the kernels that can meet ghosts behind a fused exchange: mid-tick and last kernels of
     // spring-only tilings (launch_tick_kernel decides; s->fused_unpack is never set for a tiling with tets / hinges)
     constexpr bool kCanGhost = KIND == 1 || KIND == 2;
     if (ghosts && !(kCanGhost && !D.has_quads)) throw std::runtime_error("internal: ghost-reading tile kernel requested for a launch that has none");
-    if (kCanGhost && ghosts) {
-        if (s->w_palette) SB_LAUNCH_TILE(false, true, (kCanGhost ? sbk::kHaloGhosts : sbk::kHaloNone)); else SB_LAUNCH_TILE(false, false, (kCanGhost ? sbk::kHaloGhosts : sbk::kHaloNone));
-    } else
-    if (s->w_palette) { if (D.has_quads) SB_LAUNCH_TILE(true, true, sbk::kHaloNone); else SB_LAUNCH_TILE(false, true, sbk::kHaloNone); }
-    else { if (D.has_quads) SB_LAUNCH_TILE(true, false, sbk::kHaloNone); else SB_LAUNCH_TILE(false, false, sbk::kHaloNone); }
-#undef SB_LAUNCH_TILE
+    const bool W = s->w_palette;
+    if (ghosts) {
+        if constexpr (kCanGhost) W ? launch_tile_shaped<KIND, false, true, sbk::kHaloGhosts>(s, D, sh, tiles_at_base, n_wg, A) : launch_tile_shaped<KIND, false, false, sbk::kHaloGhosts>(s, D, sh, tiles_at_base, n_wg, A);
+    } else if (sh.quads) W ? launch_tile_shaped<KIND, true, true, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A) : launch_tile_shaped<KIND, true, false, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A);
+    else W ? launch_tile_shaped<KIND, false, true, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A) : launch_tile_shaped<KIND, false, false, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A);
 }
 
 struct LaunchTimer {            // optional HIP-event pair around every launch of one tick (sb_step_profiled)
@@ -634,8 +614,8 @@ int sb_step(sb_solver *s, float dt, int32_t substeps) {
             enqueue_substeps(s, substeps, nullptr, t.fuse, t.defer_last, t.kin);
         } else {
             const int key = substeps * 8 + (t.fuse ? 1 : 0) + (t.defer_last ? 2 : 0) + (t.kin ? 4 : 0);
-            auto it = s->graphs.find(key);
-            if (it == s->graphs.end()) {
+            hipGraphExec_t exec = s->graphs.find(key);
+            if (!exec) {
                 hipGraph_t g = nullptr;
                 HIP_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
                 s->capturing = true;
@@ -649,21 +629,9 @@ int sb_step(sb_solver *s, float dt, int32_t substeps) {
                 }
                 s->capturing = false;
                 HIP_CHECK(hipStreamEndCapture(s->stream, &g));
-                hipGraphExec_t ge = nullptr;
-                hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(g);
-                if (e != hipSuccess) throw HipError(SB_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-                if (s->graphs.size() >= sb_solver::kMaxGraphs) {     // evict the least recently used executable
-                    auto old = s->graphs.begin();
-                    for (auto q = s->graphs.begin(); q != s->graphs.end(); ++q) if (q->second.last_use < old->second.last_use) old = q;
-                    HIP_CHECK(hipStreamSynchronize(s->stream));          // it may still be running
-                    (void)hipGraphExecDestroy(old->second.exec);
-                    s->graphs.erase(old);
-                }
-                it = s->graphs.emplace(key, sb_solver::CachedGraph{ge, 0}).first;
+                exec = s->graphs.add(key, g, s->stream);      // (evicts the least recently used executable beyond GraphCache::kMaxGraphs)
             }
-            it->second.last_use = ++s->graph_clock;
-            HIP_CHECK(hipGraphLaunch(it->second.exec, s->stream));
+            HIP_CHECK(hipGraphLaunch(exec, s->stream));
         }
         end_tick(s, t);
         if (calibrating && s->calib.state == 1) calibrate_after_tick(s);
@@ -765,16 +733,11 @@ int sb_debug_halo_pack(sb_solver *s, int32_t slot, float *host_out, int64_t capa
         flush_deferred(s);
         DevHalo &D = *s->halos[slot];
         const int ns = D.send_off.back();
-        const int64_t need = (int64_t)ns * (slot == 1 ? 6 : 3);
+        const int64_t need = (int64_t)ns * (int64_t)sbt::ghost_floats((size_t)slot);
         *count_floats = need;
         if (need == 0) return SB_OK;
         if (!host_out || capacity_floats < need) return fail(SB_ERR_INVALID_ARG, "sb_debug_halo_pack: buffer too small");
-        if (slot == 1)
-            hipLaunchKernelGGL(sbk::halo_pack_kernel<true>, dim3((ns + 255) / 256), dim3(256), 0, s->stream, s->pos_view(), s->d_prev.p,
-                               D.send_idx.p, s->d_sendbuf.p, ns);
-        else
-            hipLaunchKernelGGL(sbk::halo_pack_kernel<false>, dim3((ns + 255) / 256), dim3(256), 0, s->stream, s->pos_view(), s->d_prev.p,
-                               D.send_idx.p, s->d_sendbuf.p, ns);
+        launch_halo_pack(s, D, slot, s->stream);
         HIP_CHECK(hipMemcpyAsync(host_out, s->d_sendbuf.p, (size_t)need * sizeof(float), hipMemcpyDeviceToHost, s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         return SB_OK;
@@ -789,19 +752,12 @@ int sb_debug_halo_unpack(sb_solver *s, int32_t slot, const float *host_in, int64
         int rc = set_device(s); if (rc) return rc;
         DevHalo &D = *s->halos[slot];
         const int nr = D.recv_off.back();
-        const int64_t need = (int64_t)nr * (slot == 1 ? 6 : 3);
+        const int64_t need = (int64_t)nr * (int64_t)sbt::ghost_floats((size_t)slot);
         if (count_floats != need) return fail(SB_ERR_INVALID_ARG, "sb_debug_halo_unpack: wrong element count");
         if (need == 0) return SB_OK;
         if (!host_in) return fail(SB_ERR_INVALID_ARG, "sb_debug_halo_unpack: null buffer");
         HIP_CHECK(hipMemcpyAsync(s->d_recvbuf.p, host_in, (size_t)need * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        if (slot == 1 && s->fused_unpack) {
-            // (the T1 kernels read the ghosts from the receive buffer: nothing to scatter)
-        } else if (slot == 1)
-            hipLaunchKernelGGL(sbk::halo_unpack_kernel<true>, dim3((nr + 255) / 256), dim3(256), 0, s->stream, s->pos_view(), s->d_prev.p,
-                               D.recv_idx.p, s->d_recvbuf.p, nr);
-        else
-            hipLaunchKernelGGL(sbk::halo_unpack_kernel<false>, dim3((nr + 255) / 256), dim3(256), 0, s->stream, s->pos_view(), s->d_prev.p,
-                               D.recv_idx.p, s->d_recvbuf.p, nr);
+        launch_halo_unpack(s, D, slot, s->stream);
         HIP_CHECK(hipStreamSynchronize(s->stream));
         return SB_OK;
     });

@@ -2,8 +2,8 @@
 // solver object (what owns its device resources: device_handles.hpp). Nothing declared here is exported (exports.map keeps the dynamic symbol table to sb_*).
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
-// Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), schedule.hip (launches, ghost exchange, the
-// tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
+// Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), launch_shape.hpp (which tile_kernel
+// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
 // window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
@@ -91,7 +91,7 @@ bool capture_overlap_ok();      // see binding.hip
 
 }  // namespace sbi
 
-#include "device_handles.hpp"      // Event, Stream, DevBuf, HostBuf, Mirror, TableRing (need HIP_CHECK)
+#include "device_handles.hpp"      // Event, Stream, DevBuf, HostBuf, Mirror, TableRing, GraphCache (need HIP_CHECK)
 #include "render.hpp"      // the render readback's state (needs them)
 
 namespace sbi {
@@ -193,10 +193,7 @@ struct sb_solver {
     std::vector<std::unique_ptr<DevHalo>> halos;   // indexed by halo slot
     sbk::TickParams tp_host{};
     bool tp_valid = false;
-    struct CachedGraph { hipGraphExec_t exec; uint64_t last_use; };
-    std::map<int, CachedGraph> graphs;         // key = substeps * 8 + (1: tick starts with the fused kernel) + (2: last kernel deferred) + (4: that kernel carries kinematic targets)
-    uint64_t graph_clock = 0;                  // least recently used entry is evicted beyond kMaxGraphs (a host that varies substeps)
-    static constexpr size_t kMaxGraphs = 8;
+    sbi::GraphCache graphs;          // sb_step's executables; key = substeps * 8 + (1: tick starts with the fused kernel) + (2: last kernel deferred) + (4: that kernel carries kinematic targets)
     // Lazy tick boundary: the last kernel of a tick (rounds + collide + velocity write) is deferred; if the next tick
     // has the same parameters it is FUSED with that tick's first kernel into one ordinary mid-tick kernel, otherwise
     // (or whenever state is read or written) it is flushed first. Results are identical either way.
@@ -306,7 +303,6 @@ struct sb_solver {
         if (comm_stream) (void)hipStreamSynchronize(comm_stream);
         if (render.copy_stream) (void)hipStreamSynchronize(render.copy_stream);
         // 2. the graph executables before the communicator: captured RCCL launches hold references into it
-        for (auto &g : graphs) (void)hipGraphExecDestroy(g.second.exec);
         graphs.clear();
         // 3. the communicator before the streams it was used on (members: they go after this body)
         if (comm) (void)sbi::rccl(false).CommDestroy(comm);
