@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void kinematic_scatter_kernel(float *pos_xyz, 
     pos_xyz[o] = targets[3 * (size_t)k]; pos_xyz[o + 1] = targets[3 * (size_t)k + 1]; pos_xyz[o + 2] = targets[3 * (size_t)k + 2];
 }
 
-// The same targets handed to the fused first kernel of the next tick instead (tile_kernel KIND 5): entry k goes to its particle's slot.
+// The same targets handed to the fused first kernel of the next tick instead (tile_kernel kKindMidKinematic): entry k goes to its particle's slot.
 __global__ __launch_bounds__(256) void kinematic_fill_kernel(const int32_t *kin_map, float *kin_target, const int32_t *idx, const float *targets, int count) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= count) return;

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stream_codec.hpp"
+
 namespace sbk {
 
 struct TickParams {           // SPEC.md §2 host-side scalars, uploaded once per (dt, S)
@@ -14,44 +16,46 @@ struct TickParams {           // SPEC.md §2 host-side scalars, uploaded once pe
     float pad[2];
 };
 
+// The six launch kinds of tile_kernel (its first template parameter; an int, so the kernels' mangled names carry the number):
+//   kKindFirst (first kernel of a tick)   : MARK: v from the velocity array, integrate; the tile's rounds
+//   kKindMid (every other substep)        : the tile's rounds (finish substep s-1), MARK: v = (x-xprev)/h, integrate (start substep s),
+//                                           the same rounds again
+//   kKindLast (after the last substep)    : the tile's rounds, MARK: write v, stop
+//   kKindLayer (T2 layer, every substep)  : the tile's rounds once, no MARK; the particles come from an explicit list
+//   kKindPeek (peek at the tick's end)    : what kKindLast would leave as positions (the tile's rounds + collide), written to a side
+//                                           array; nothing of the state is written, so the deferred last kernel of a tick can still be
+//                                           fused with the first kernel of the next one (render readback, schedule.hip peek_positions)
+//   kKindMidKinematic (a tick's fused first kernel when kinematic targets are pending): kKindMid, and between the velocity of the
+//                                           substep that ended and the integrate of the next one a particle with w = 0 that has a
+//                                           target takes it
+constexpr int kKindFirst = 0, kKindMid = 1, kKindLast = 2, kKindLayer = 3, kKindPeek = 4, kKindMidKinematic = 5;
+constexpr bool kind_is_kinematic(int k) { return k == kKindMidKinematic; }
+constexpr int kind_base(int k) { return kind_is_kinematic(k) ? kKindMid : k; }                                  // the kind whose schedule k follows
+constexpr bool kind_has_mark(int k) { return k != kKindLayer; }
+constexpr bool kind_rounds_before_mark(int k) { return k != kKindFirst; }                                       // (kKindLayer: its only pass)
+constexpr bool kind_rounds_after_mark(int k) { return k == kKindFirst || kind_base(k) == kKindMid; }
+constexpr bool kind_ends_tick(int k) { return k == kKindLast || k == kKindPeek; }                               // MARK stops at the collided positions
+constexpr bool kind_reads_prev(int k) { return kind_base(k) == kKindMid || k == kKindLast; }                    // v = (x - xprev) / h
+constexpr bool kind_writes_peek(int k) { return k == kKindPeek; }                                               // else: the state arrays
+constexpr bool kind_may_read_ghosts(int k) { return k == kKindMid || k == kKindLast; }                          // T1 launches of a lattice-type plan
+constexpr bool kind_gathers(int k) { return k == kKindLayer; }                                                  // particles from the gather list, not from runs
+
 // One LDS tile (or pack of tiles) = one workgroup. 128 B, read with scalar loads.
-// The tile's constraint stream lives at stream[s_begin ...], 16-byte aligned, in dwords:
-//   [round words, padded to 4] [rest-length palette, padded to 4] [rounds' data]
-// group word: bits 0-9 distance, 10-19 volume, 20-29 bending constraint count (each <= 256), bit 30 = the distance slots
-// are dictionary-coded. A group's constraints share no particle (one barrier per group). Its data: the distance slots,
-// count x {i | j<<16, rest length}, or -- when a tile's distance constraints use at most 256 distinct rest lengths
-// (regular meshes) -- count x {i | j<<12 | palette index<<24} (one dword each) with the values in the tile's palette,
-// padded to 4 dwords; then the volume slots, then the bending slots, each {i0|i1<<16, i2|i3<<16, rest.x, rest.y}.
+// The tile's constraint stream lives at stream[s_begin ...]; its layout and every bit field of it: stream_codec.hpp.
 struct TileDesc {
     int32_t n_local, run_count, n_rounds;
-    int32_t gather_begin;      // KIND 3 (T2 tiles): the tile's particles are gather[gather_begin .. +n_local) instead of runs
+    int32_t gather_begin;      // kKindLayer (T2 tiles): the tile's particles are gather[gather_begin .. +n_local) instead of runs
     uint32_t s_begin;          // dword offset of the tile's stream
     uint32_t s_hdr;            // dwords of round words + palette (each padded to 4): round data starts at s_begin + s_hdr
     uint32_t s_len;            // total dwords (multiple of 4)
-    uint32_t packed_lanes;     // 0, or 128 / 256: LANE-PACKED slots (see kLanePack* / kWidePack*) for workgroups of that many lanes -- the launch must use that width
+    uint32_t packed_lanes;     // 0, or 128 / 256: LANE-PACKED slots (stream_codec.hpp kLanePack* / kWidePack*) for workgroups of that many lanes -- the launch must use that width
     int32_t run_overflow;      // runs beyond kInlineRuns live at runs_overflow[run_overflow ...]
     int32_t n_pal;             // palette entries (0 = no dictionary coding), stored after the round words
-    int32_t n_steps;           // wave items per wave (meshes with tets / hinges; 0 = none), see kItem* below
+    int32_t n_steps;           // wave items per wave (meshes with tets / hinges; 0 = none), stream_codec.hpp kItem*
     uint32_t s_items;          // dword offset (from s_begin) of the items: kItemWaves runs of n_steps dwords, inside the header
     int2 runs[10];             // {first particle (device numbering), first tile-local index}; unused entries: {0, INT_MAX}
 };
 constexpr int kInlineRuns = 10;
-// Lane-packed slots (round 3, second session). A register-resident spring tile run by 128-lane workgroups gives every lane two slots in
-// each of its (at most three) rounds and keeps them in registers for both passes; the slots need 9 + 9 bits of tile-local indices and a
-// palette index. Stored as ONE 16-byte word per lane -- six 21-bit fields {i:9 | j:9 | palette:3}, field 2 r + u = the lane's slot u of
-// round r (constraint lane + 128 u of that round; beyond the round's count the field is 0) -- the tile's data is 2 KiB instead of 3 KiB
-// (4 bytes per slot), it arrives in the lane's first window load and never touches LDS. The host decides per tile (tables_host.cpp pack_form).
-// A tile whose slots are NOT dictionary-coded (per-spring rest lengths) packs the same way with its rest values behind the index words:
-// [128 x 16 B index word][128 x 16 B: rest of fields 0..3][128 x 8 B: rest of fields 4, 5] = 40 bytes per lane instead of 48
-// (n_pal == 0 marks this form; only in the kernels that read inverse masses as floats, WPAL = false -- the host packs accordingly).
-constexpr int kLanePackLanes = 128, kLanePackRounds = 3, kLanePackFieldBits = 21, kLanePackMaxPalette = 8;
-constexpr uint32_t kLanePackDwordsCompact = 4 * kLanePackLanes, kLanePackDwordsFull = 10 * kLanePackLanes;
-// The same for 256-lane workgroups (round 4): a lane has ONE slot per round, so three 21-bit fields = ONE 8-byte word per lane, field r = the
-// lane's slot of round r (constraint `lane` of that round) -- again 2 KiB per 512-particle tile instead of 3 KiB, loaded by the lane itself
-// with the first batch, never staged in LDS. Dictionary-coded tiles only. For the launches between the 512-lane and the 128-lane regimes:
-// mid-size meshes (128^3: 4 096 tiles) and the ranks of a partitioned solver (256^3 on 8 ranks: 4 096 tiles each).
-constexpr int kWidePackLanes = 256;
-constexpr uint32_t kWidePackDwords = 2 * kWidePackLanes;
 constexpr int kWide8MaxTiles = 768;     // launches of at most this many spring-only small tiles run 512-lane workgroups (schedule.hip launch_tile)
 // Register-resident programs (tile_kernel): a tile of at most this many distance rounds keeps its slots and rest lengths in registers.
 // Build switches of A/B timing variants (make EXTRA=-D...): the HOST reads the same constants when it decides which tiles to lane-pack
@@ -69,17 +73,7 @@ constexpr bool kRegFullSlots = false;
 constexpr bool kRegFullSlots = true;
 #endif
 constexpr bool kLanePackDecodable = kRegRoundsNarrow >= kLanePackRounds;       // else the host emits no lane-packed tile at all
-// Wave items (meshes with tets / hinges, 4-wave tiles): the host deals every group's work to the four waves ahead of time --
-// hinges first, then tets (16 four-lane constraints per wave), then springs (64 per wave), boustrophedon over the rows of
-// a group -- and stores for every wave one dword per STEP (= one row of one group): what to project, how many, where the
-// slots lie in the tile's data, and whether the group ends here (workgroup barrier). The kernel's loop over a list is then a
-// v_readlane, three bit-field extracts and one uniform branch per step instead of decoding the group word, the window test
-// and the slot arithmetic (90 scalar instructions and a dozen branches per group on the critical path of every group).
-constexpr int kItemWaves = 4;        // dealt for 4-wave tiles (8 with SB_QUAD_LANES=512)
-constexpr uint32_t kItemIdle = 0, kItemDistCompact = 1, kItemDistFull = 2, kItemVolume = 3, kItemBending = 4;
-constexpr int kItemCountShift = 3, kItemBarrierBit = 10, kItemOffsetShift = 11;     // type:3 | count:7 | barrier:1 | dword offset:21
 constexpr int kMaxRoundsLds = 128;   // round words cached in LDS; longer programs read them from memory
-constexpr int kMaxPalette = 256;     // rest-length dictionary entries per tile
 
 // Positions in HBM: packed xyz (12 B) + the static inverse mass in a side array (never rewritten).
 typedef float f32x3_t __attribute__((ext_vector_type(3)));
@@ -95,12 +89,12 @@ struct TileArgs {
     const uint8_t *w8;        // WPAL kernels: index of the particle's inverse mass in wpal (1 B instead of 4 B per read)
     const float *wpal;        // kMaxMassPalette entries
     float *prev;              // packed xyz
-    float *vel;               // packed xyz (read by KIND 0, written by KIND 2)
+    float *vel;               // packed xyz (read by kKindFirst, written by kKindLast)
     const TileDesc *tiles;
     const int2 *runs_overflow;
     const uint32_t *stream;
     const TickParams *tp;
-    const int32_t *gather;    // KIND 3: particle lists of the sparse T2 tiles (device numbering)
+    const int32_t *gather;    // kKindLayer: particle lists of the sparse T2 tiles (device numbering)
     int32_t max_local;        // LDS carve: [max_local float4][rounds_dwords][pal_dwords][win_dwords][16 spare bytes]
     int32_t rounds_dwords;    // round words cached in LDS (multiple of 4, <= kMaxRoundsLds); longer programs read memory
     int32_t pal_dwords;       // largest rest-length dictionary of the tiling, padded to 4 (0 = none)
@@ -114,10 +108,10 @@ struct TileArgs {
     // ghost order) instead of from the arrays -- the unpack kernel between the exchange and this launch is gone
     const float *ghost_src;
     int32_t n_owned;
-    // KIND 4 (peek): where the tick-end positions of the launch's tiles go (packed xyz, device numbering); the state arrays stay as
+    // kKindPeek: where the tick-end positions of the launch's tiles go (packed xyz, device numbering); the state arrays stay as
     // they are
     float *peek_out;
-    // KIND 5 (kinematic targets inside the fused tick boundary): kin_map[g] = slot of pinned particle g (-1: free particle),
+    // kKindMidKinematic (kinematic targets inside the fused tick boundary): kin_map[g] = slot of pinned particle g (-1: free particle),
     // kin_target[3 slot ..] = its pending target or NaN; the lane that applies a target writes NaN back
     const int32_t *kin_map;
     float *kin_target;

@@ -221,7 +221,7 @@ void launch_tile_shaped(const sb_solver *s, const DevTiling &D, const sbt::Launc
     throw std::runtime_error("internal: no tile kernel is built for the launch shape asked for");
 }
 
-// `table` (KIND 4 only): a descriptor table of its own -- copies of some of D's descriptors -- instead of D's tiles [tile_begin, tile_end)
+// `table` (kKindPeek only): a descriptor table of its own -- copies of some of D's descriptors -- instead of D's tiles [tile_begin, tile_end)
 template <int KIND>
 void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = -1, int halo = sbk::kHaloNone, const sbk::TileDesc *table = nullptr) {
     const bool ghosts = halo == sbk::kHaloGhosts;
@@ -236,15 +236,15 @@ void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = 
     A.item_waves = D.item_waves;
     A.store_through = tile_end - tile_begin <= s->store_through_max_tiles ? 3 : s->store_through_large;
     A.ghost_src = ghosts ? s->d_recvbuf.p : nullptr; A.n_owned = (int32_t)s->n_owned;
-    A.peek_out = KIND == 4 ? s->d_peek.p : nullptr;
-    A.kin_map = KIND == 5 ? s->d_kin_map.p : nullptr; A.kin_target = KIND == 5 ? s->d_kin_target.p : nullptr;
+    A.peek_out = sbk::kind_writes_peek(KIND) ? s->d_peek.p : nullptr;
+    A.kin_map = sbk::kind_is_kinematic(KIND) ? s->d_kin_map.p : nullptr; A.kin_target = sbk::kind_is_kinematic(KIND) ? s->d_kin_target.p : nullptr;
     A.max_local = D.max_local; A.win_dwords = D.win_dwords; A.tile_base = tile_begin; A.pal_dwords = D.pal_dwords; A.rounds_dwords = D.rounds_dwords;
     const sbk::TileDesc *tiles_at_base = table ? table : D.tiles.p + tile_begin;      // the two preloaded kernel arguments (tile_kernel)
     const int n_wg = tile_end - tile_begin;
     const sbt::LaunchShape sh = sbt::tile_launch_shape(D, s->tile_lanes, s->quad_lanes, s->narrow_min_tiles, n_wg, ghosts);
     // the ghost-reading variant exists for the kernels that can meet ghosts behind a fused exchange: mid-tick and last kernels of
     // spring-only tilings (launch_tick_kernel decides; s->fused_unpack is never set for a tiling with tets / hinges)
-    constexpr bool kCanGhost = KIND == 1 || KIND == 2;
+    constexpr bool kCanGhost = sbk::kind_may_read_ghosts(KIND);
     if (ghosts && !(kCanGhost && !D.has_quads)) throw std::runtime_error("internal: ghost-reading tile kernel requested for a launch that has none");
     const bool W = s->w_palette;
     if (ghosts) {
@@ -272,10 +272,10 @@ void launch_tick_kernel(sb_solver *s, int it, int substeps, LaunchTimer *lt, int
     DevTiling &D = s->tiling[tl];
     if (lt && D.n_tiles) lt->begin(it == 0 ? 2 + (int)s->gcolours.size() : (it == substeps ? 3 + (int)s->gcolours.size() : tl));
     const int halo_in = s->fused_unpack && tl == 1 ? sbk::kHaloGhosts : sbk::kHaloNone;      // T1 tiles read their ghosts straight from the receive buffer
-    if (it == 0) launch_tile<0>(s, D, tile_begin, tile_end);
-    else if (it < substeps && kin) launch_tile<5>(s, D, tile_begin, tile_end);        // (the fused first kernel of a tick, with kinematic targets: a T0 launch, owned particles only)
-    else if (it < substeps) launch_tile<1>(s, D, tile_begin, tile_end, halo_in);
-    else launch_tile<2>(s, D, tile_begin, tile_end, halo_in);
+    if (it == 0) launch_tile<sbk::kKindFirst>(s, D, tile_begin, tile_end);
+    else if (it < substeps && kin) launch_tile<sbk::kKindMidKinematic>(s, D, tile_begin, tile_end);        // (the fused first kernel of a tick, with kinematic targets: a T0 launch, owned particles only)
+    else if (it < substeps) launch_tile<sbk::kKindMid>(s, D, tile_begin, tile_end, halo_in);
+    else launch_tile<sbk::kKindLast>(s, D, tile_begin, tile_end, halo_in);
     if (lt && D.n_tiles) lt->end();
 }
 
@@ -285,7 +285,7 @@ void launch_t2_layer(sb_solver *s, int layer, LaunchTimer *lt, bool with_halo = 
     if (with_halo) halo_exchange(s, 2 + (int)s->gcolours.size() + layer);
     if (rg.second <= rg.first) return;
     if (lt) lt->begin(4 + (int)s->gcolours.size());
-    launch_tile<3>(s, s->tiling[2], rg.first, rg.second);
+    launch_tile<sbk::kKindLayer>(s, s->tiling[2], rg.first, rg.second);
     if (lt) lt->end();
 }
 
@@ -448,7 +448,7 @@ void stage_kinematic_for_fusion(sb_solver *s) {
 
 // ---- peek: tick-end positions without completing the tick ------------------------------------------------------------------------
 // While the last kernel K_S of a tick is deferred, the positions the tick ends with are K_S's rounds + collide applied to the state
-// in memory. tile_kernel<4> computes exactly that -- same tiles, same programs, same inputs, hence the same bits -- into d_peek and
+// in memory. tile_kernel<kKindPeek> computes exactly that -- same tiles, same programs, same inputs, hence the same bits -- into d_peek and
 // leaves the state alone, so the next sb_step still fuses K_S with its first kernel (one launch instead of two) and a render
 // readback after every tick no longer costs a whole extra pass over the mesh. On every rank of a partitioned solver too (round 4): the
 // held-back kernel runs on T0 tiles, which hold owned particles only and have no exchange in front of them.
@@ -489,8 +489,8 @@ void peek_positions(sb_solver *s, bool subset) {
     if (!s->d_peek.p) s->d_peek.alloc((size_t)s->n_local * 3, s->dev_bytes);
     if (subset) {
         if (s->n_peek_tiles <= 0) return;       // (no tile holds a wanted particle: nothing is launched, nothing is counted)
-        launch_tile<4>(s, D, 0, s->n_peek_tiles, sbk::kHaloNone, s->peek_tiles.p);
-    } else launch_tile<4>(s, D);
+        launch_tile<sbk::kKindPeek>(s, D, 0, s->n_peek_tiles, sbk::kHaloNone, s->peek_tiles.p);
+    } else launch_tile<sbk::kKindPeek>(s, D);
     HIP_CHECK(hipGetLastError());
     ++s->n_peeks;
 }

@@ -2,7 +2,7 @@
 // solver object (what owns its device resources: device_handles.hpp). Nothing declared here is exported (exports.map keeps the dynamic symbol table to sb_*).
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
-// Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), tables.hip (their upload), launch_shape.hpp (which tile_kernel
+// Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), stream_codec.hpp (the bit layout of the tile constraint stream: the builder's encoders, the kernels' and the validator's decoders), tables.hip (their upload), launch_shape.hpp (which tile_kernel
 // instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
 // window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
@@ -106,7 +106,7 @@ struct DevHalo {                 // one halo slot: who we talk to and which part
 struct DevTiling : sbt::TilingScalars {
     DevBuf<sbk::TileDesc> tiles;
     DevBuf<int2> runs_overflow;
-    DevBuf<uint32_t> stream;     // per tile: [round words][rest-length dictionary][round data], see kernel_types.hpp
+    DevBuf<uint32_t> stream;     // per tile: [round words][rest-length dictionary][round data], see stream_codec.hpp
     DevBuf<int32_t> gather;      // T2: particle lists of the tiles (local numbering)
 };
 
@@ -129,7 +129,7 @@ enum class TileRange : uint8_t { All, T0Boundary, T0Interior, T1Interior, T1Boun
 struct TickStep {
     StepKind kind;
     TileRange range;        // Tile: which of the rank's tiles
-    bool kin;               // Tile: the fused first kernel carries kinematic targets (tile_kernel KIND 5)
+    bool kin;               // Tile: the fused first kernel carries kinematic targets (tile_kernel kKindMidKinematic)
     int it, substeps;       // Tile: kernel K_it of a tick of `substeps` substeps
     int index;              // T2Layer: layer; GColour: colour; *Exchange: halo slot
 };
@@ -262,7 +262,7 @@ struct sb_solver {
     std::vector<uint32_t> kin_seen; uint32_t kin_stamp = 0;     // duplicate-id check of sb_set_kinematic_positions
     std::vector<int32_t> local_of_old;     // the rank's numbering -> device numbering (-1: not held), built at first use (readback.hip)
     // Targets are PENDING until the next tick starts: if that tick's first kernel also finishes the tick before (lazy tick boundary),
-    // they travel into it (tile_kernel KIND 5 applies them between the old tick's velocity and the new tick's integrate) and the
+    // they travel into it (tile_kernel kKindMidKinematic applies them between the old tick's velocity and the new tick's integrate) and the
     // fusion is kept; any other way across the boundary (state read or written, parameters changed, first tick) completes the old
     // tick and scatters them onto the positions (materialise_kinematic).
     int kin_pending = -1, kin_pending_count = 0;      // ring slot that holds them, or -1
@@ -273,7 +273,7 @@ struct sb_solver {
     bool kin_fuse = true;                  // !SB_TUNE_NO_KIN_FUSE (A/B: pending targets always complete the previous tick first)
     // impulses (sb_apply_impulses, impulse.hip): the sparse kernels' tables travel like the kinematic targets, one table per call
     sbi::TableRing<4> imp_ring;
-    // Peek (world == 1): a position read while the tick's last kernel is deferred runs tile_kernel<4> -- the same rounds + collide on
+    // Peek (world == 1): a position read while the tick's last kernel is deferred runs tile_kernel<kKindPeek> -- the same rounds + collide on
     // the same inputs, written to d_peek instead of the state -- so the deferred kernel can still be fused with the next tick's first
     // one. A render-set-only readback peeks only at the T0 tiles that hold a render particle (peek_tiles: copies of their descriptors).
     DevBuf<float> d_peek;                  // packed xyz per local particle; only the peeked tiles' entries are ever written or read

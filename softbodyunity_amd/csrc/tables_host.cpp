@@ -3,7 +3,7 @@
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 //
 // Map of the file (a stage reads its arguments and writes its result; nothing else is shared):
-//   helpers            float_bits, layer_of, GroupCounts / decode_group / group_data_dwords, slot_field, xcd_position
+//   helpers            float_bits, layer_of, pack_field, xcd_position (the stream's bit fields: stream_codec.hpp)
 //   build_state        pack_state, mass_palette
 //   build_tiling       boundary_order          T0 boundary tiles first, T1 boundary tiles last (world > 1)
 //                      pack_tiles              best fit of under-full tiles into workgroups, by layer / boundary class
@@ -39,19 +39,11 @@ int layer_of(const sbp::Plan &P, int32_t plan_tile) {
     return ly;
 }
 
-// group word: bits 0-9 distance, 10-19 volume, 20-29 bending constraint count (kernel_types.hpp TileDesc)
-struct GroupCounts { int32_t cnt[3]; };
-GroupCounts decode_group(uint32_t w) { return {{(int32_t)(w & 1023u), (int32_t)((w >> 10) & 1023u), (int32_t)((w >> 20) & 1023u)}}; }
-
-// dwords of a group's distance slots, padded to 16 bytes: one dword per dictionary-coded slot, two per full slot.
-// Mirrors `dsize` of tile_kernel.hip.hpp (the group walk of tile_kernel): the wave items' offsets are the kernel's.
-uint32_t group_data_dwords(uint32_t n_dist, bool compact) { return compact ? ((n_dist + 3u) & ~3u) : ((2u * n_dist + 3u) & ~3u); }
-
-// the 21-bit field {i:9 | j:9 | palette:3} of the lane-packed and the wide-packed words (kernel_types.hpp kLanePackFieldBits)
-uint64_t slot_field(uint32_t idx, uint32_t pal_index, const char *what) {
-    const uint32_t i = idx & 0xffffu, j = idx >> 16;
-    if (i > 511u || j > 511u || pal_index > 7u) throw std::runtime_error(what);
-    return (uint64_t)(i | (j << 9) | (pal_index << 18));
+// the 21-bit field of the lane-packed and the wide-packed words for the index pair `idx`
+uint32_t pack_field(uint32_t idx, uint32_t pal_index, const char *what) {
+    const sbk::IndexPair p = sbk::decode_index_pair(idx);
+    if (!sbk::pack_field_fits(p.i, p.j, pal_index)) throw std::runtime_error(what);
+    return sbk::encode_pack_field(p.i, p.j, pal_index);
 }
 
 // The tile that workgroup `wg` of a launch of `n` workgroups reads. Must match the XCD remap at the head of tile_kernel
@@ -303,11 +295,12 @@ void zip_rounds(const TilingEnv &E, const std::vector<int32_t> &members, std::ve
         for (size_t m = 0; m < members.size(); ++m) {
             const sbp::Tile &T = E.tile(members[m]);
             if (next[m] >= T.n_rounds) continue;
-            const GroupCounts c = decode_group(E.G.rounds[T.round_begin + next[m]]);
-            if (R.cnt[0] + c.cnt[0] > sbp::kRoundThreads || R.cnt[1] + c.cnt[1] > sbp::kRoundThreads || R.cnt[2] + c.cnt[2] > sbp::kRoundThreads) continue;
-            R.parts.push_back({(int32_t)m, {c.cnt[0], c.cnt[1], c.cnt[2]}, dk[m], qk[m]});
-            dk[m] += c.cnt[0]; qk[m] += c.cnt[1] + c.cnt[2];
-            for (int t = 0; t < 3; ++t) R.cnt[t] += c.cnt[t];
+            const sbk::GroupWord gw = sbk::decode_group_word(E.G.rounds[T.round_begin + next[m]]);      // (the plan's round words have the stream's layout)
+            const int32_t c[3] = {(int32_t)gw.n_dist, (int32_t)gw.n_vol, (int32_t)gw.n_bend};
+            if (R.cnt[0] + c[0] > sbp::kRoundThreads || R.cnt[1] + c[1] > sbp::kRoundThreads || R.cnt[2] + c[2] > sbp::kRoundThreads) continue;
+            R.parts.push_back({(int32_t)m, {c[0], c[1], c[2]}, dk[m], qk[m]});
+            dk[m] += c[0]; qk[m] += c[1] + c[2];
+            for (int t = 0; t < 3; ++t) R.cnt[t] += c[t];
             ++next[m];
         }
         if (R.parts.empty()) break;
@@ -329,7 +322,7 @@ std::vector<uint32_t> rest_dictionary(const TilingEnv &E, const std::vector<int3
     }
     std::sort(vals.begin(), vals.end());
     vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-    if (!((int)vals.size() <= sbk::kMaxPalette && n_local <= 4096)) vals.clear();
+    if (!((int)vals.size() <= sbk::kMaxPalette && n_local <= sbk::kCompactMaxLocal)) vals.clear();
     return vals;
 }
 uint32_t palette_index(const std::vector<uint32_t> &pal, uint32_t rest_bits) { return (uint32_t)(std::lower_bound(pal.begin(), pal.end(), rest_bits) - pal.begin()); }
@@ -345,7 +338,7 @@ void emit_wave_items(const TilingEnv &E, const std::vector<PackRound> &prog, boo
     bool fits = true;
     for (const PackRound &R : prog) {
         const uint32_t nd = (uint32_t)R.cnt[0], nv = (uint32_t)R.cnt[1], nb = (uint32_t)R.cnt[2];
-        const uint32_t dsize = group_data_dwords(nd, compact), qoff = off + dsize;
+        const uint32_t dsize = sbk::group_data_dwords(nd, compact), qoff = off + dsize;
         const int n_wb = (int)((nb + 3) >> 2), n_wv = (int)((nv + 15) >> 4), n_wd = (int)((nd + 63) >> 6);
         const int n_slots = n_wb + n_wv + n_wd, rows = std::max(1, (n_slots + item_waves - 1) / item_waves);
         for (int row = 0; row < rows; ++row)
@@ -358,11 +351,10 @@ void emit_wave_items(const TilingEnv &E, const std::vector<PackRound> &prog, boo
                     const uint32_t c0 = 64u * (uint32_t)(sw - n_wb - n_wv);
                     type = compact ? sbk::kItemDistCompact : sbk::kItemDistFull; cnt = std::min(64u, nd - c0); o = off + (compact ? c0 : 2u * c0);
                 }
-                if (o >= (1u << (32 - sbk::kItemOffsetShift))) fits = false;
-                it[wave].push_back(type | (cnt << sbk::kItemCountShift) | (row + 1 == rows ? 1u << sbk::kItemBarrierBit : 0u) |
-                                   (o << sbk::kItemOffsetShift));
+                if (!sbk::item_offset_fits(o)) fits = false;
+                it[wave].push_back(sbk::encode_item(type, cnt, row + 1 == rows, o));
             }
-        off += dsize + 4u * (nv + nb);
+        off += sbk::group_dwords(nd, nv + nb, compact);
     }
     if (!fits) return;
     td.n_steps = (int32_t)it[0].size();
@@ -385,7 +377,7 @@ void for_each_distance_slot(const TilingEnv &E, const PackSlots &S, F &&f) {
     for (size_t r = 0; r < S.prog.size(); ++r) {
         int32_t c = 0;
         for (const Part &pt : S.prog[r].parts) {
-            const uint32_t b = (uint32_t)S.base[pt.member], b2 = b | (b << 16);       // added to both 16-bit local indices
+            const uint32_t b2 = sbk::index_pair_offset((uint32_t)S.base[pt.member]);
             for (int64_t k = pt.first_d; k < pt.first_d + pt.cnt[0]; ++k, ++c) f((int)r, c, E.G.t_dist[k] + b2, float_bits(E.in.dist_rest[E.G.t_dist_id[k]]));
         }
     }
@@ -396,16 +388,11 @@ void emit_lane_packed(const TilingEnv &E, const PackSlots &S, std::vector<uint32
     const bool compact = S.compact();
     std::vector<uint32_t> words(compact ? sbk::kLanePackDwordsCompact : sbk::kLanePackDwordsFull, 0u);
     for_each_distance_slot(E, S, [&](int r, int32_t c, uint32_t idx, uint32_t rb) {
-        const uint64_t f = slot_field(idx, compact ? palette_index(S.pal, rb) : 0u, "internal: lane-packed slot out of range");
+        const uint32_t f = pack_field(idx, compact ? palette_index(S.pal, rb) : 0u, "internal: lane-packed slot out of range");
         const int lane = c % sbk::kLanePackLanes, u = c / sbk::kLanePackLanes, fld = 2 * r + u;
-        const int bit = sbk::kLanePackFieldBits * fld, w0 = bit >> 5, sh = bit & 31;
-        uint32_t *wd = &words[4 * (size_t)lane];
-        wd[w0] |= (uint32_t)(f << sh);
-        if (sh + sbk::kLanePackFieldBits > 32) wd[w0 + 1] |= (uint32_t)(f >> (32 - sh));
-        if (compact) return;
+        sbk::set_lane_word_field(&words[(size_t)sbk::kLaneWordDwords * (size_t)lane], fld, f);
         // the slot's rest length: fields 0..3 in the second 16-byte sweep, 4 and 5 in the 8-byte one
-        if (fld < 4) words[4 * (size_t)sbk::kLanePackLanes + 4 * (size_t)lane + (size_t)fld] = rb;
-        else words[8 * (size_t)sbk::kLanePackLanes + 2 * (size_t)lane + (size_t)(fld - 4)] = rb;
+        if (!compact) words[sbk::lane_pack_rest_dword((uint32_t)lane, (uint32_t)fld)] = rb;
     });
     stream.insert(stream.end(), words.begin(), words.end());
 }
@@ -415,9 +402,7 @@ void emit_wide_packed(const TilingEnv &E, const PackSlots &S, std::vector<uint32
     std::vector<uint32_t> words(sbk::kWidePackDwords, 0u);
     for_each_distance_slot(E, S, [&](int r, int32_t c, uint32_t idx, uint32_t rb) {
         if (c >= sbk::kWidePackLanes) throw std::runtime_error("internal: wide-packed slot out of range");
-        const uint64_t f = slot_field(idx, palette_index(S.pal, rb), "internal: wide-packed slot out of range") << (sbk::kLanePackFieldBits * r);
-        words[2 * (size_t)c] |= (uint32_t)f;
-        words[2 * (size_t)c + 1] |= (uint32_t)(f >> 32);
+        sbk::set_wide_word_field(&words[(size_t)sbk::kWideWordDwords * (size_t)c], r, pack_field(idx, palette_index(S.pal, rb), "internal: wide-packed slot out of range"));
     });
     stream.insert(stream.end(), words.begin(), words.end());
 }
@@ -427,17 +412,18 @@ void emit_slots(const TilingEnv &E, const PackSlots &S, size_t s0, std::vector<u
     const sbp::Tiling &G = E.G;
     for (const PackRound &R : S.prog) {
         for (const Part &pt : R.parts) {
-            const uint32_t b = (uint32_t)S.base[pt.member], b2 = b | (b << 16);
+            const uint32_t b2 = sbk::index_pair_offset((uint32_t)S.base[pt.member]);
             for (int64_t k = pt.first_d; k < pt.first_d + pt.cnt[0]; ++k) {
                 const uint32_t idx = G.t_dist[k] + b2, rb = float_bits(E.in.dist_rest[G.t_dist_id[k]]);
-                if (S.compact()) stream.push_back((idx & 0xffffu) | ((idx >> 16) << 12) | (palette_index(S.pal, rb) << 24));
+                const sbk::IndexPair p = sbk::decode_index_pair(idx);
+                if (S.compact()) stream.push_back(sbk::encode_compact_slot(p.i, p.j, palette_index(S.pal, rb)));
                 else { stream.push_back(idx); stream.push_back(rb); }
             }
         }
         pad16(stream, s0);
         for (int t = 1; t < 3; ++t)
             for (const Part &pt : R.parts) {
-                const uint32_t b = (uint32_t)S.base[pt.member], b2 = b | (b << 16);
+                const uint32_t b2 = sbk::index_pair_offset((uint32_t)S.base[pt.member]);
                 const int64_t kb = pt.first_q + (t == 2 ? pt.cnt[1] : 0);      // a member's group lists its tets, then its hinges
                 for (int64_t k = kb; k < kb + pt.cnt[t]; ++k) {
                     if (G.t_quad_type[k] != t) throw std::runtime_error("internal: group layout");
@@ -466,7 +452,7 @@ uint32_t pack_form(const TilingEnv &E, const PackSlots &S, int32_t n_local, int6
     if (E.packed_lanes == sbk::kWidePackLanes && S.compact() && (int)S.pal.size() <= sbk::kLanePackMaxPalette) {
         // (the packed form is 2 KiB whatever the tile holds: only where that is LESS than 4 bytes per slot -- full-size tiles, not rim packs)
         uint32_t unpacked = 0;
-        for (const PackRound &R : prog) { if (R.cnt[0] > sbk::kWidePackLanes) return 0; unpacked += ((uint32_t)R.cnt[0] + 3u) & ~3u; }
+        for (const PackRound &R : prog) { if (R.cnt[0] > sbk::kWidePackLanes) return 0; unpacked += sbk::group_data_dwords((uint32_t)R.cnt[0], true); }
         return unpacked > sbk::kWidePackDwords ? (uint32_t)sbk::kWidePackLanes : 0u;
     }
     return 0;
@@ -486,8 +472,7 @@ void build_pack(const TilingEnv &E, const std::vector<int32_t> &members, Piece &
     const size_t s0 = stream.size();
     const std::vector<uint32_t> pal = rest_dictionary(E, members, n.n_dist, td.n_local);
     const bool compact = !pal.empty();
-    for (const PackRound &R : prog)      // group word: counts per type, bit 30 = dictionary-coded distance slots
-        stream.push_back((uint32_t)R.cnt[0] | ((uint32_t)R.cnt[1] << 10) | ((uint32_t)R.cnt[2] << 20) | (compact ? 1u << 30 : 0u));
+    for (const PackRound &R : prog) stream.push_back(sbk::encode_group_word((uint32_t)R.cnt[0], (uint32_t)R.cnt[1], (uint32_t)R.cnt[2], compact));
     pad16(stream, s0);
     if (stream.size() == s0) stream.insert(stream.end(), 4, 0u);   // empty program: keep 16 readable bytes
     td.n_pal = (int32_t)pal.size();
@@ -601,8 +586,8 @@ int64_t share_programs(std::vector<sbk::TileDesc> &tiles, std::vector<uint32_t> 
 int32_t tile_cost(const sbk::TileDesc &td, const std::vector<uint32_t> &stream, bool has_quads, int32_t item_waves) {
     int32_t c = 0;
     for (int32_t r = 0; r < td.n_rounds; ++r) {
-        const GroupCounts g = decode_group(stream[(size_t)td.s_begin + (size_t)r]);
-        const int32_t nd = g.cnt[0], nv = g.cnt[1], nb = g.cnt[2];
+        const sbk::GroupWord g = sbk::decode_group_word(stream[(size_t)td.s_begin + (size_t)r]);
+        const int32_t nd = (int32_t)g.n_dist, nv = (int32_t)g.n_vol, nb = (int32_t)g.n_bend;
         if (has_quads) {       // rows of wave slots (as dealt for the wave items), a step with a hinge counts double
             const int nw = std::max(1, (int)item_waves ? (int)item_waves : 4);
             c += std::max(1, (((nd + 63) >> 6) + ((nv + 15) >> 4) + ((nb + 3) >> 2) + nw - 1) / nw) + (nb > 0 ? 1 : 0);

@@ -8,16 +8,10 @@ namespace sbk {
 
 // One workgroup = one tile (or one pack of under-full tiles, tables_host.cpp pack_tiles) of THREADS lanes; a tile owns one
 // constraint list, cut into rounds of at most kRoundSlots independent constraints (plan.hpp):
-//   KIND 0 (first kernel of a tick)  : MARK: v from the velocity array, integrate; the tile's rounds
-//   KIND 1 (every other substep)     : the tile's rounds (finish substep s-1), MARK: v = (x-xprev)/h, integrate
-//                                      (start substep s), the same rounds again
-//   KIND 2 (after the last substep)  : the tile's rounds, MARK: write v, stop
-//   KIND 3 (T2 layer, every substep)  : the tile's rounds once, no MARK; the particles come from an explicit list
-//   KIND 5 (a tick's fused first kernel when kinematic targets are pending): KIND 1, and between the velocity of the substep that
-//                                      ended and the integrate of the next one a particle with w = 0 that has a target takes it
-//   KIND 4 (peek at the tick's end)   : what KIND 2 would leave as positions (the tile's rounds + collide), written to a side
-//                                      array; nothing of the state is written, so the deferred last kernel of a tick can still
-//                                      be fused with the first kernel of the next one (render readback, schedule.hip peek_positions)
+//   what a launch does with the list is its kind (kernel_types.hpp kKind*: which passes run around the MARK step, what MARK does);
+//   the bit fields of the stream are decoded with the accessors of stream_codec.hpp.
+// The body runs in this order: descriptor (XCD remap) -> particle ownership -> every load of the tile, issued together, staged in LDS ->
+// ONE of three round engines (register-resident rounds | wave items | the windowed group walk), each "rounds, MARK, rounds" -> store.
 // Particles AND the tile's constraint stream are staged in LDS with wide coalesced loads issued together,
 // so a tile pays the HBM latency once; rounds then run LDS-to-LDS with one barrier each. Each lane keeps
 // ownership of up to PPT particles for the MARK step and projects kRoundSlots / THREADS constraints per round.
@@ -26,17 +20,32 @@ namespace sbk {
 // __syncthreads() would also drain vmcnt, i.e. wait for the xprev stores of the MARK step.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// distance slot c of the slots at `slots` (dictionary-coded or full, stream_codec.hpp): its two tile-local particles and its rest length
+__device__ __forceinline__ void decode_compact_distance(uint32_t e, const float *s_pal, int &i, int &k, float &L0) { i = compact_slot_i(e); k = compact_slot_j(e); L0 = s_pal[compact_slot_pal(e)]; }
+__device__ __forceinline__ void decode_full_distance(const uint2 e, int &i, int &k, float &L0) { i = pair_i(e.x); k = pair_j(e.x); L0 = __uint_as_float(e.y); }
+__device__ __forceinline__ void read_distance_slot(const uint32_t *slots, int c, bool compact, const float *s_pal, int &i, int &k, float &L0) {
+    if (compact) decode_compact_distance(slots[c], s_pal, i, k, L0);
+    else decode_full_distance(*reinterpret_cast<const uint2 *>(slots + kFullSlotDwords * c), i, k, L0);
+}
+
+// a four-vertex slot as lane q of a quad sees it: the LDS float offsets of component q of its four particles (stream_codec.hpp)
+__device__ __forceinline__ void quad_slot_offsets(const uint4 &e, int q, int &o0, int &o1, int &o2, int &o3) {
+    o0 = 4 * (int)pair_i(e.x) + q; o1 = 4 * (int)pair_j(e.x) + q;
+    o2 = 4 * (int)pair_i(e.y) + q; o3 = 4 * (int)pair_j(e.y) + q;
+}
+
 // Register budget (HIP: second launch-bound = waves per SIMD). LDS allows ~14 tiles per CU, so aim for that many waves.
 template <bool QUADS, int THREADS> constexpr int kWavesPerSimd = QUADS ? (THREADS == 64 ? 3 : (THREADS == 512 ? 2 : 4)) : (THREADS == 256 ? 8 : (THREADS == 128 ? 6 : 4));   // 128 lanes: 7 waves (72 VGPRs) measured 1 % slower, 8 spill
 // WPAL = inverse masses are read as one-byte palette indices (the palette entry comes from another lane by ds_bpermute).
 template <int KIND_, bool QUADS, int THREADS, int PPT, bool WPAL, int HALO = kHaloNone>
-// (KIND 5 -- one launch per tick, and only when kinematic targets are pending -- gets one wave per SIMD less: its MARK step holds more
+// (kKindMidKinematic -- one launch per tick, and only when kinematic targets are pending -- gets one wave per SIMD less: its MARK step holds more
 // live values, and under the ordinary bound it spilled 4 .. 14 registers)
 __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ == 5 && !QUADS ? 1 : 0))) void tile_kernel(const TileDesc *tiles_at_base, int n_workgroups, TileArgs A) {
-    // KIND 5 = KIND 1 whose MARK step also applies pending kinematic targets (see TileArgs::kin_map): an instantiation of its own, so the
+    // kKindMidKinematic = kKindMid whose MARK step also applies pending kinematic targets (see TileArgs::kin_map): an instantiation of its own, so the
     // ordinary mid-tick kernel carries nothing of it
-    constexpr int KIND = KIND_ == 5 ? 1 : KIND_;
-    constexpr bool KIN = KIND_ == 5;
+    // (convention below: the predicates of kernel_types.hpp take KIND_ as it came; a comparison with one kind uses the folded KIND)
+    constexpr int KIND = kind_base(KIND_);
+    constexpr bool KIN = kind_is_kinematic(KIND_);
     constexpr bool GHOSTS = HALO == kHaloGhosts;
     // The first two arguments (3 dwords) are preloaded into SGPRs at dispatch (-mllvm -amdgpu-kernarg-preload-count=3, Makefile):
     // the descriptor fetch starts with the kernel instead of behind the kernel-argument load (one memory round trip less on the
@@ -78,7 +87,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     // INT_MAX there, so the last run that starts at or before l is found by a compare/select chain on scalars
     // (a loop with a scalar branch per run and slot cost ~400 SALU instructions per wave BEFORE the first load).
     int g[PPT];
-    if (KIND == 3) {
+    if (kind_gathers(KIND_)) {
 #pragma unroll
         for (int m = 0; m < PPT; ++m) {
             const int l = tid + m * kTileThreads;
@@ -106,8 +115,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     // ---- the stretch of the stream this kernel needs, staged through an LDS window -----------------
     // virtual program: rounds 0..R-1 (finish the previous substep), MARK, rounds 0..R-1 again (start the next)
     const int R = n_rounds_all;
-    const int v_begin = KIND == 0 ? R : 0;
-    const int v_end = KIND == 3 ? R : (KIND == 2 || KIND == 4 ? R + 1 : 2 * R + 1);
+    const int v_begin = kind_rounds_before_mark(KIND_) ? 0 : R;
+    const int v_end = !kind_has_mark(KIND_) ? R : (kind_rounds_after_mark(KIND_) ? 2 * R + 1 : R + 1);
     const uint32_t d_lo = td.s_hdr;
     const uint32_t d_hi = td.s_len;
     const uint32_t win = (uint32_t)A.win_dwords;
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
         X[m].x = px[0]; X[m].y = px[1]; X[m].z = px[2];
         if (WPAL) { wi[m] = A.w8[A.w_uniform ? 0 : gc]; X[m].w = 0.0f; } else { wi[m] = 0; X[m].w = A.pos.w[gc]; }
         pvx[m] = pvy[m] = pvz[m] = 0.0f;
-        if (KIND != 0 && KIND != 3 && KIND != 4) {
+        if (kind_reads_prev(KIND_)) {
             const float *pp = ghost ? px + 3 : A.prev + 3 * (size_t)gc;
             pvx[m] = pp[0]; pvy[m] = pp[1]; pvz[m] = pp[2];
         }
@@ -159,7 +168,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     // v_readlane (no LDS round trip at the head of each round): +3 % at 64^3, +1 % at 256^3
     const bool rounds_in_lanes = n_rounds_all <= 64;
     const uint32_t rwl = tstream[max(min(tid & 63, n_rounds_all - 1), 0)];
-    // wave items (see kItem*): lane l of a wave holds the wave's step l (tiles without items re-read round word 0)
+    // wave items (stream_codec.hpp kItem*): lane l of a wave holds the wave's step l (tiles without items re-read round word 0)
     uint32_t itreg = 0;
     if (QUADS && kTileThreads == 64 * A.item_waves) {
         const int ns = td.n_steps;
@@ -247,19 +256,19 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             if (g[m] >= 0) {
                 const int l = tid + m * kTileThreads;
                 float4 P = lds_pos[l];
-                if (KIND != 0 && tp.plane_on && P.w > 0.0f) {   // collide: end of the substep that just finished
+                if (KIND != kKindFirst && tp.plane_on && P.w > 0.0f) {   // collide: end of the substep that just finished
                     float a = tp.pnx * P.x, b = tp.pny * P.y, c = tp.pnz * P.z;
                     float pen = ((a + b) + c) - tp.pd;
                     if (pen < 0.0f) {
                         float dx = pen * tp.pnx, dy = pen * tp.pny, dz = pen * tp.pnz;
                         P.x = P.x - dx; P.y = P.y - dy; P.z = P.z - dz;
-                        if (KIND == 2 || KIND == 4) lds_pos[l] = P;
+                        if (kind_ends_tick(KIND_)) lds_pos[l] = P;
                     }
                 }
-                if (KIND == 4) continue;     // (a peek ends with the collided positions: no velocity, no state write)
+                if (KIND == kKindPeek) continue;     // (a peek ends with the collided positions: no velocity, no state write)
                 float vx, vy, vz;
                 const size_t o = 3 * (size_t)g[m];
-                if (KIND == 0) {
+                if (KIND == kKindFirst) {
                     vx = A.vel[o + 0]; vy = A.vel[o + 1]; vz = A.vel[o + 2];
                 } else {
                     float dx = P.x - pvx[m], dy = P.y - pvy[m], dz = P.z - pvz[m];
@@ -275,7 +284,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                         if (tx == tx) { P.x = tx; P.y = ty; P.z = tz; moved = true; t[0] = __int_as_float(0x7fc00000); }
                     }
                 }
-                if (KIND == 2) {
+                if (KIND == kKindLast) {
                     A.vel[o + 0] = vx; A.vel[o + 1] = vy; A.vel[o + 2] = vz;
                 } else {
                     if (A.store_through & 1) store3_through(A.prev + o, P.x, P.y, P.z);
@@ -290,6 +299,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             }
     };
 
+    // ---- engine 1, register-resident rounds --------------------------------------------------------------------------------------
     // Short programs of dictionary-coded distance groups (every tile of a regular mesh: 3 groups) keep their constraint
     // slots and rest lengths in registers: one batch of LDS reads ahead of the first round instead of two dependent LDS
     // round trips (slot, then palette entry) at the head of every round, in both passes. Same constraints, same order.
@@ -307,16 +317,18 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             for (int r = 0; r < kRegRounds; ++r) {
                 rcnt[r] = 0;
                 if (r < n_rounds_all) {
-                    rcnt[r] = (int)((uint32_t)__builtin_amdgcn_readlane((int)rwl, r) & 1023u);
+                    rcnt[r] = (int)group_dist_count((uint32_t)__builtin_amdgcn_readlane((int)rwl, r));
                     if (kCPL == 2 && lane_packed) {
                         // the lane's own 16-byte word, loaded with the window's first sweep: fields 2 r and 2 r + 1
 #pragma unroll
                         for (int u = 0; u < kCPL; ++u) {
+                            // (where field 2 r + u lies in the word: stream_codec.hpp pack_field_pos, spelled out -- through a function the
+                            // compiler orders the kernel's instructions differently)
                             const int bit = kLanePackFieldBits * (2 * r + u), w0 = bit >> 5, sh = bit & 31;
                             const uint32_t lo = wv[0][w0] >> sh;
-                            const uint32_t hi = (sh + kLanePackFieldBits > 32) ? (wv[0][w0 + 1 < 4 ? w0 + 1 : 3] << ((32 - sh) & 31)) : 0u;
-                            const uint32_t f = (lo | hi) & ((1u << kLanePackFieldBits) - 1u);
-                            rs[r][u] = (f & 511u) | (((f >> 9) & 511u) << 12) | ((f >> 18) << 24);
+                            const uint32_t hi = (sh + kLanePackFieldBits > 32) ? (wv[0][w0 + 1 < kLaneWordDwords ? w0 + 1 : kLaneWordDwords - 1] << ((32 - sh) & 31)) : 0u;
+                            const uint32_t f = (lo | hi) & kLanePackFieldMask;
+                            rs[r][u] = compact_slot_of_pack_field(f);
                             if (!WPAL) {     // (full slots: the rest length travels beside the index word; compact tiles overwrite rl from the palette below)
                                 const int fld = 2 * r + u;
                                 rl[r][u] = __uint_as_float(fld < 4 ? wv[1][fld < 4 ? fld : 0] : wc[fld >= 4 ? fld - 4 : 0]);
@@ -324,27 +336,24 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                         }
                     } else if (kCPL == 1 && wide_packed) {
                         // the lane's own 8-byte word: field r (three 21-bit fields)
-                        const uint64_t two = (uint64_t)wp.x | ((uint64_t)wp.y << 32);
-                        const uint32_t f = (uint32_t)(two >> (kLanePackFieldBits * (r < kLanePackRounds ? r : 0))) & ((1u << kLanePackFieldBits) - 1u);
-                        rs[r][0] = (f & 511u) | (((f >> 9) & 511u) << 12) | ((f >> 18) << 24);
+                        rs[r][0] = compact_slot_of_pack_field(wide_word_field(wp.x, wp.y, r < kLanePackRounds ? r : 0));
                     } else if (tile_compact) {
 #pragma unroll
                         for (int u = 0; u < kCPL; ++u) {
                             const int c = tid + u * kTileThreads;
                             rs[r][u] = cbuf[o + (c < rcnt[r] ? c : 0)];
                         }
-                        o += ((uint32_t)rcnt[r] + 3u) & ~3u;
+                        o += compact_data_dwords((uint32_t)rcnt[r]);
                     } else {
 #pragma unroll
                         for (int u = 0; u < kCPL; ++u) {
                             const int c = tid + u * kTileThreads;
                             const uint2 e = *reinterpret_cast<const uint2 *>(cbuf + o + 2 * (c < rcnt[r] ? c : 0));
-                            // re-code the 16 | 16 bit index pair as the 12 | 12 bit form the rounds decode (tiles of this path hold at
-                            // most 512 particles)
-                            rs[r][u] = (e.x & 0xfffu) | ((e.x >> 16) << 12);
+                            // the index pair as the slot word the rounds decode (tiles of this path hold at most 512 particles)
+                            rs[r][u] = compact_slot_of_pair(e.x);
                             rl[r][u] = __uint_as_float(e.y);
                         }
-                        o += (2u * (uint32_t)rcnt[r] + 3u) & ~3u;
+                        o += full_data_dwords((uint32_t)rcnt[r]);
                     }
                 } else {
 #pragma unroll
@@ -355,13 +364,13 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #pragma unroll
                 for (int r = 0; r < kRegRounds; ++r)
 #pragma unroll
-                    for (int u = 0; u < kCPL; ++u) rl[r][u] = s_pal[rs[r][u] >> 24];
+                    for (int u = 0; u < kCPL; ++u) rl[r][u] = s_pal[compact_slot_pal(rs[r][u])];
             }
         }
         auto reg_round = [&](const uint32_t (&e)[kCPL], const float (&L0)[kCPL], int cnt) {
             if (kCPL == 1) {
                 if (tid < cnt) {
-                    const int i = e[0] & 0xfffu, k = (e[0] >> 12) & 0xfffu;
+                    const int i = compact_slot_i(e[0]), k = compact_slot_j(e[0]);
                     float4 a = lds_pos[i], b = lds_pos[k];
                     if (project_distance(a, b, L0[0], tp.at_d)) { lds_pos[i] = a; lds_pos[k] = b; }
                 }
@@ -372,7 +381,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #pragma unroll
                 for (int u = 0; u < kCPL; ++u) {
                     con[u] = tid + u * kTileThreads < cnt;
-                    ci[u] = e[u] & 0xfffu; ck[u] = (e[u] >> 12) & 0xfffu;
+                    ci[u] = compact_slot_i(e[u]); ck[u] = compact_slot_j(e[u]);
                     ca[u] = *reinterpret_cast<const f32x4 *>(lds_pos + ci[u]);
                     cb[u] = *reinterpret_cast<const f32x4 *>(lds_pos + ck[u]);
                 }
@@ -397,17 +406,17 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #else
         constexpr bool kRunRounds = true;
 #endif
-        if (KIND != 0 && kRunRounds) {
+        if (kind_rounds_before_mark(KIND_) && kRunRounds) {
 #pragma unroll
             for (int r = 0; r < kRegRounds; ++r) if (r < n_rounds_all) reg_round(rs[r], rl[r], rcnt[r]);
         }
-        if (KIND != 3) { mark_step(); lds_barrier(); }
-        if ((KIND == 0 || KIND == 1) && kRunRounds) {
+        if (kind_has_mark(KIND_)) { mark_step(); lds_barrier(); }
+        if (kind_rounds_after_mark(KIND_) && kRunRounds) {
 #pragma unroll
             for (int r = 0; r < kRegRounds; ++r) if (r < n_rounds_all) reg_round(rs[r], rl[r], rcnt[r]);
         }
     } else if (QUADS && kTileThreads == 64 * A.item_waves && td.n_steps > 0 && d_hi - d_lo <= win) {
-        // ---- wave items: the whole data of the tile is in the window, every wave walks its own list of steps ----------------
+        // ---- engine 2, wave items: the whole data of the tile is in the window, every wave walks its own list of steps --------
         const int n_steps = td.n_steps;
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
         const uint32_t *items = tstream + td.s_items + (uint32_t)(wave * n_steps);
@@ -422,9 +431,9 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             for (int st = 0; st < n_steps; ++st) {
                 if ((st & 63) == 0 && st > 0) itreg = items[min(st + lane, n_steps - 1)];
                 const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)itreg, st & 63);
-                const uint32_t type = it & 7u;
-                const int cnt = (int)((it >> kItemCountShift) & 127u);
-                const uint32_t *slots = cbuf + (it >> kItemOffsetShift);
+                const uint32_t type = item_type(it);
+                const int cnt = (int)item_count(it);
+                const uint32_t *slots = cbuf + item_offset(it);
                 if (type == kItemBending) {
                     // sixteen lanes per hinge (see project_bending_row): every quad of the row reads the four particles, quad k
                     // writes particle k back
@@ -432,8 +441,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     if (c < cnt) {
                         const uint4 e = *reinterpret_cast<const uint4 *>(slots + 4 * c);
                         const int k = (lane >> 2) & 3;
-                        const int o0 = 4 * (int)(e.x & 0xffffu) + q, o1 = 4 * (int)(e.x >> 16) + q;
-                        const int o2 = 4 * (int)(e.y & 0xffffu) + q, o3 = 4 * (int)(e.y >> 16) + q;
+                        int o0, o1, o2, o3;
+                        quad_slot_offsets(e, q, o0, o1, o2, o3);
                         const float P[4] = {lds_f[o0], lds_f[o1], lds_f[o2], lds_f[o3]};
                         float Xk = k == 0 ? P[0] : (k == 1 ? P[1] : (k == 2 ? P[2] : P[3]));
                         const int ok_off = k == 0 ? o0 : (k == 1 ? o1 : (k == 2 ? o2 : o3));
@@ -450,8 +459,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     const int c = lane >> 2;
                     if (c < cnt) {
                         const uint4 e = *reinterpret_cast<const uint4 *>(slots + 4 * c);
-                        const int o0 = 4 * (int)(e.x & 0xffffu) + q, o1 = 4 * (int)(e.x >> 16) + q;
-                        const int o2 = 4 * (int)(e.y & 0xffffu) + q, o3 = 4 * (int)(e.y >> 16) + q;
+                        int o0, o1, o2, o3;
+                        quad_slot_offsets(e, q, o0, o1, o2, o3);
                         float P[4] = {lds_f[o0], lds_f[o1], lds_f[o2], lds_f[o3]};
 #if defined(SB_ABLATE) && SB_ABLATE == 2
                         const bool ok = true; P[0] += __uint_as_float(e.z); P[1] -= P[2]; P[3] += P[0];
@@ -464,13 +473,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     if (lane < cnt) {
                         int i, k;
                         float L0;
-                        if (type == kItemDistCompact) {
-                            const uint32_t e = slots[lane];
-                            i = e & 0xfffu; k = (e >> 12) & 0xfffu; L0 = s_pal[e >> 24];
-                        } else {
-                            const uint2 e = *reinterpret_cast<const uint2 *>(slots + 2 * lane);
-                            i = e.x & 0xffffu; k = e.x >> 16; L0 = __uint_as_float(e.y);
-                        }
+                        read_distance_slot(slots, lane, type == kItemDistCompact, s_pal, i, k, L0);
                         float4 a = lds_pos[i], b = lds_pos[k];
 #if defined(SB_ABLATE) && SB_ABLATE == 2
                         a.x += L0; b.x -= tp.at_d; lds_pos[i] = a; lds_pos[k] = b;
@@ -479,13 +482,14 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #endif
                     }
                 }
-                if (it & (1u << kItemBarrierBit)) lds_barrier();
+                if (item_barrier(it)) lds_barrier();
             }
         };
-        if (KIND != 0) run_pass();
-        if (KIND != 3) { mark_step(); lds_barrier(); }
-        if (KIND == 0 || KIND == 1) run_pass();
+        if (kind_rounds_before_mark(KIND_)) run_pass();
+        if (kind_has_mark(KIND_)) { mark_step(); lds_barrier(); }
+        if (kind_rounds_after_mark(KIND_)) run_pass();
     } else {
+    // ---- engine 3, windowed group walk: group after group through the LDS window, refilled where the tile's data is longer ------------
     uint32_t off = d_lo;    // dword offset (from the tile's stream start) of the current group's data
 #if defined(SB_ABLATE) && SB_ABLATE == 1   // timing experiment only: memory traffic without the rounds
     for (int v = v_begin; v < v_end; v += 100000) {
@@ -499,10 +503,9 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
         if (rounds_in_lanes) w = (uint32_t)__builtin_amdgcn_readlane((int)rwl, __builtin_amdgcn_readfirstlane(r));
         else if (rounds_in_lds) w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_rounds[r]);
         else w = (uint32_t)__builtin_amdgcn_readfirstlane((int)tstream[r]);
-        // group word: distance | volume << 10 | bending << 20 constraint counts, bit 30 = dictionary-coded distance slots
-        const int cnt = w & 1023u, n_vol = (w >> 10) & 1023u, n_bend = (w >> 20) & 1023u;
-        const bool compact = (w >> 30) & 1u;
-        const uint32_t dsize = compact ? ((cnt + 3u) & ~3u) : ((2u * cnt + 3u) & ~3u);
+        const int cnt = group_dist_count(w), n_vol = group_vol_count(w), n_bend = group_bend_count(w);
+        const bool compact = group_is_compact(w);
+        const uint32_t dsize = compact ? compact_data_dwords(cnt) : full_data_dwords(cnt);
         const uint32_t size = dsize + 4u * (uint32_t)(n_vol + n_bend);
         if (off + size > win_lo + win || off < win_lo) {   // refill the window (uniform; rare for small tiles)
             lds_barrier();
@@ -535,8 +538,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     const int c = (bend ? sw : sw - n_wb) * 16 + (lane >> 2);
                     if (c < (bend ? n_bend : n_vol)) {
                         const uint4 e = *reinterpret_cast<const uint4 *>(qbase + 4 * (bend ? n_vol + c : c));
-                        const int o0 = 4 * (int)(e.x & 0xffffu) + q, o1 = 4 * (int)(e.x >> 16) + q;
-                        const int o2 = 4 * (int)(e.y & 0xffffu) + q, o3 = 4 * (int)(e.y >> 16) + q;
+                        int o0, o1, o2, o3;
+                        quad_slot_offsets(e, q, o0, o1, o2, o3);
                         float P[4] = {lds_f[o0], lds_f[o1], lds_f[o2], lds_f[o3]};
                         const bool ok = bend ? project_bending_quad(P, __uint_as_float(e.z), __uint_as_float(e.w), tp.at_b, q)
                                              : project_volume_quad(P, __uint_as_float(e.z), tp.at_v);
@@ -547,13 +550,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     if (c < cnt) {
                         int i, k;
                         float L0;
-                        if (compact) {
-                            const uint32_t e = base[c];
-                            i = e & 0xfffu; k = (e >> 12) & 0xfffu; L0 = s_pal[e >> 24];
-                        } else {
-                            const uint2 e = *reinterpret_cast<const uint2 *>(base + 2 * c);
-                            i = e.x & 0xffffu; k = e.x >> 16; L0 = __uint_as_float(e.y);
-                        }
+                        read_distance_slot(base, c, compact, s_pal, i, k, L0);
                         float4 a = lds_pos[i], b = lds_pos[k];
                         if (project_distance(a, b, L0, tp.at_d)) { lds_pos[i] = a; lds_pos[k] = b; }
                     }
@@ -563,13 +560,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             if (tid < cnt) {
                 int i, k;
                 float L0;
-                if (compact) {
-                    const uint32_t e = base[tid];
-                    i = e & 0xfffu; k = (e >> 12) & 0xfffu; L0 = s_pal[e >> 24];
-                } else {
-                    const uint2 e = *reinterpret_cast<const uint2 *>(base + 2 * tid);
-                    i = e.x & 0xffffu; k = e.x >> 16; L0 = __uint_as_float(e.y);
-                }
+                read_distance_slot(base, tid, compact, s_pal, i, k, L0);
                 float4 a = lds_pos[i], b = lds_pos[k];
 #if defined(SB_ABLATE) && SB_ABLATE == 2   // timing experiment only: LDS traffic + barriers without the arithmetic
                 a.x += L0; b.x -= tp.at_d;
@@ -591,7 +582,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     const int c = tid + u * kTileThreads;
                     con[u] = c < cnt;
                     const uint2 e = *reinterpret_cast<const uint2 *>(base + 2 * (con[u] ? c : 0));
-                    ci[u] = e.x & 0xffffu; ck[u] = e.x >> 16; cL0[u] = __uint_as_float(e.y);
+                    decode_full_distance(e, ci[u], ck[u], cL0[u]);
                 }
             } else {
                 uint32_t ce[kCPL];
@@ -602,7 +593,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                     ce[u] = base[con[u] ? c : 0];
                 }
 #pragma unroll
-                for (int u = 0; u < kCPL; ++u) { ci[u] = ce[u] & 0xfffu; ck[u] = (ce[u] >> 12) & 0xfffu; cL0[u] = s_pal[ce[u] >> 24]; }
+                for (int u = 0; u < kCPL; ++u) decode_compact_distance(ce[u], s_pal, ci[u], ck[u], cL0[u]);
             }
 #pragma unroll
             for (int u = 0; u < kCPL; ++u) {
@@ -638,7 +629,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     for (int m = 0; m < PPT; ++m)
         if (g[m] >= 0) {
             const float4 P = lds_pos[tid + m * kTileThreads];
-            if (KIND == 4) { float *o = A.peek_out + 3 * (size_t)g[m]; o[0] = P.x; o[1] = P.y; o[2] = P.z; }
+            if (kind_writes_peek(KIND_)) { float *o = A.peek_out + 3 * (size_t)g[m]; o[0] = P.x; o[1] = P.y; o[2] = P.z; }
             else if (A.store_through & 2) store3_through(A.pos.xyz + 3 * (size_t)g[m], P.x, P.y, P.z);
             else pv_store(A.pos, g[m], P);
         }

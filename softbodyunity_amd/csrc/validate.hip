@@ -56,20 +56,21 @@ int sb_debug_validate(sb_solver *s, int32_t inject_fault, sb_validate_report *ou
                     std::vector<uint32_t> words((size_t)std::max(td.n_rounds, 1));
                     HIP_CHECK(hipMemcpy(words.data(), D.stream.p + td.s_begin, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
                     uint32_t off = td.s_hdr;
-                    if (td.packed_lanes && td.n_rounds > 0 && (words[0] & 1023u) >= 2) {      // lane-packed: lane 0's word over lane 1's
+                    if (td.packed_lanes && td.n_rounds > 0 && sbk::group_dist_count(words[0]) >= 2) {      // lane-packed: lane 0's word over lane 1's
                         uint32_t *base = s_copy.p + td.s_begin + off;
-                        const size_t lane_dwords = td.packed_lanes == (uint32_t)sbk::kWidePackLanes ? 2 : 4;
+                        const size_t lane_dwords = td.packed_lanes == (uint32_t)sbk::kWidePackLanes ? sbk::kWideWordDwords : sbk::kLaneWordDwords;
                         HIP_CHECK(hipMemcpy(base + lane_dwords, base, lane_dwords * sizeof(uint32_t), hipMemcpyDeviceToDevice));
                         planted = true;
                     }
                     for (int r = 0; r < td.n_rounds && !planted && !td.packed_lanes; ++r) {
-                        const uint32_t w = words[(size_t)r], cnt = w & 1023u, nq = ((w >> 10) & 1023u) + ((w >> 20) & 1023u);
-                        const bool compact = (w >> 30) & 1u;
-                        const uint32_t dsize = compact ? ((cnt + 3u) & ~3u) : ((2u * cnt + 3u) & ~3u);
+                        const sbk::GroupWord gw = sbk::decode_group_word(words[(size_t)r]);
+                        const uint32_t cnt = gw.n_dist, nq = gw.n_vol + gw.n_bend;
+                        const bool compact = gw.compact;
+                        const uint32_t dsize = sbk::group_data_dwords(cnt, compact);
                         uint32_t *base = s_copy.p + td.s_begin + off;
-                        if (cnt >= 2) { HIP_CHECK(hipMemcpy(base + (compact ? 1 : 2), base, (compact ? 1 : 2) * sizeof(uint32_t), hipMemcpyDeviceToDevice)); planted = true; }
-                        else if (nq >= 2) { HIP_CHECK(hipMemcpy(base + dsize + 4, base + dsize, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice)); planted = true; }
-                        off += dsize + 4u * nq;
+                        if (cnt >= 2) { const uint32_t sd = compact ? 1u : (uint32_t)sbk::kFullSlotDwords; HIP_CHECK(hipMemcpy(base + sd, base, sd * sizeof(uint32_t), hipMemcpyDeviceToDevice)); planted = true; }
+                        else if (nq >= 2) { HIP_CHECK(hipMemcpy(base + dsize + sbk::kQuadSlotDwords, base + dsize, sbk::kQuadSlotDwords * sizeof(uint32_t), hipMemcpyDeviceToDevice)); planted = true; }
+                        off += sbk::group_dwords(cnt, nq, compact);
                     }
                 }
                 if (!planted) return fail(SB_ERR_STATE, "sb_debug_validate: no group with two constraints of one type to plant the fault in");

@@ -10,7 +10,7 @@ namespace sbk {
 // The only race this design can have is two constraints of one group (or two tiles of one launch) touching the same particle. The
 // planner's output is checked on the host (tests/test_plan.py); THIS kernel checks what the tile kernels actually read -- the uploaded
 // descriptors, run tables / particle lists, group words, dictionary-coded or full slots, four-vertex slots and wave items, after
-// packing, lane dealing and cost ordering -- with the tile kernels' own decoding rules. One workgroup per device tile.
+// packing, lane dealing and cost ordering -- with the tile kernels' own decoding rules (stream_codec.hpp). One workgroup per device tile.
 __global__ __launch_bounds__(kValidateThreads) void validate_tiles_kernel(const TileDesc *tiles, int tile_begin, const int2 *runs_overflow, const uint32_t *stream,
                                                                          const int32_t *gather, int use_gather, int n_particles, int item_waves,
                                                                          int32_t *owner, ValidateCounters *out) {
@@ -65,26 +65,24 @@ __global__ __launch_bounds__(kValidateThreads) void validate_tiles_kernel(const 
         // (kWidePack*) -- one 8-byte word per lane, field r = slot lane of round r
         const uint32_t P = td.packed_lanes;
         const bool wide = P == (uint32_t)kWidePackLanes;
-        const uint32_t lane_dwords = wide ? 2u : 4u;
+        const uint32_t lane_dwords = wide ? (uint32_t)kWideWordDwords : (uint32_t)kLaneWordDwords;
         // (n_pal == 0: the full form of the 128-lane packing, rest lengths behind the index words)
         if ((P != (uint32_t)kLanePackLanes && !wide) || td.n_rounds > kLanePackRounds || td.n_pal < 0 || td.n_pal > kLanePackMaxPalette || td.n_local > kSmallTile ||
             (wide && td.n_pal == 0) ||
             td.s_hdr + (wide ? kWidePackDwords : (td.n_pal > 0 ? kLanePackDwordsCompact : kLanePackDwordsFull)) > td.s_len) { if (tid == 0) flag(3, -1); walk_ok = false; }
         for (int r = 0; walk_ok && r < td.n_rounds; ++r) {
-            const uint32_t w = ts[r];
-            const uint32_t cnt = w & 1023u;
-            if (cnt > (wide ? P : 2u * P) || ((w >> 10) & 0xfffffu) != 0u) { if (tid == 0) flag(3, r); walk_ok = false; break; }
+            const GroupWord gw = decode_group_word(ts[r]);
+            const uint32_t cnt = gw.n_dist;
+            if (cnt > (wide ? P : 2u * P) || (gw.n_vol | gw.n_bend) != 0u) { if (tid == 0) flag(3, r); walk_ok = false; break; }
             for (int q = tid; q < kLargeTile / 32; q += kValidateThreads) bitmap[q] = 0;
             __syncthreads();
             for (uint32_t c = tid; c < cnt; c += kValidateThreads) {
-                const uint32_t lane = c % P, u = c / P, bit = (uint32_t)kLanePackFieldBits * (wide ? (uint32_t)r : 2u * (uint32_t)r + u), w0 = bit >> 5, sh = bit & 31u;
+                const uint32_t lane = c % P, u = c / P;
                 const uint32_t *wd = ts + td.s_hdr + lane_dwords * lane;
-                uint64_t two = (uint64_t)wd[w0] | ((uint64_t)(w0 + 1 < lane_dwords ? wd[w0 + 1] : 0u) << 32);
-                const uint32_t f = (uint32_t)(two >> sh) & ((1u << kLanePackFieldBits) - 1u);
-                const uint32_t p0 = f & 511u, p1 = (f >> 9) & 511u;
-                if ((f >> 18) >= (uint32_t)max(td.n_pal, 1)) flag(0, r);
+                const CompactSlot f = decode_pack_field(packed_word_field(wd, lane_dwords, wide ? (uint32_t)r : 2u * (uint32_t)r + u));
+                if (f.pal >= (uint32_t)max(td.n_pal, 1)) flag(0, r);
                 for (int e = 0; e < 2; ++e) {
-                    const uint32_t p = e ? p1 : p0;
+                    const uint32_t p = e ? f.j : f.i;
                     if (p >= (uint32_t)td.n_local) flag(0, r);
                     else if (atomicOr(&bitmap[p >> 5], 1u << (p & 31)) & (1u << (p & 31))) flag(1, r);
                 }
@@ -94,11 +92,11 @@ __global__ __launch_bounds__(kValidateThreads) void validate_tiles_kernel(const 
         }
     } else
     for (int r = 0; walk_ok && r < td.n_rounds; ++r) {
-        const uint32_t w = ts[r];
-        const uint32_t cnt = w & 1023u, n_vol = (w >> 10) & 1023u, n_bend = (w >> 20) & 1023u;
-        const bool compact = (w >> 30) & 1u;
-        const uint32_t dsize = compact ? ((cnt + 3u) & ~3u) : ((2u * cnt + 3u) & ~3u);
-        const uint32_t size = dsize + 4u * (n_vol + n_bend);
+        const GroupWord gw = decode_group_word(ts[r]);
+        const uint32_t cnt = gw.n_dist, n_vol = gw.n_vol, n_bend = gw.n_bend;
+        const bool compact = gw.compact;
+        const uint32_t dsize = group_data_dwords(cnt, compact);
+        const uint32_t size = group_dwords(cnt, n_vol + n_bend, compact);
         if (off + size > td.s_len || cnt > (uint32_t)kRoundSlots || n_vol > (uint32_t)kRoundSlots || n_bend > (uint32_t)kRoundSlots ||
             (compact && td.n_pal <= 0)) { if (tid == 0) flag(3, r); walk_ok = false; break; }
         for (int q = tid; q < kLargeTile / 32; q += kValidateThreads) bitmap[q] = 0;
@@ -108,14 +106,12 @@ __global__ __launch_bounds__(kValidateThreads) void validate_tiles_kernel(const 
             if (atomicOr(&bitmap[p >> 5], 1u << (p & 31)) & (1u << (p & 31))) flag(1, r);
         };
         for (uint32_t c = tid; c < cnt; c += kValidateThreads) {
-            uint32_t i, k;
-            if (compact) { const uint32_t e = ts[off + c]; i = e & 0xfffu; k = (e >> 12) & 0xfffu; if ((e >> 24) >= (uint32_t)td.n_pal) flag(0, r); }
-            else { const uint32_t e = ts[off + 2 * c]; i = e & 0xffffu; k = e >> 16; }
-            mark(i); mark(k);
+            if (compact) { const CompactSlot e = decode_compact_slot(ts[off + c]); if (e.pal >= (uint32_t)td.n_pal) flag(0, r); mark(e.i); mark(e.j); }
+            else { const IndexPair e = decode_index_pair(ts[off + kFullSlotDwords * c]); mark(e.i); mark(e.j); }
         }
         for (uint32_t c = tid; c < n_vol + n_bend; c += kValidateThreads) {
-            const uint32_t e0 = ts[off + dsize + 4 * c], e1 = ts[off + dsize + 4 * c + 1];
-            mark(e0 & 0xffffu); mark(e0 >> 16); mark(e1 & 0xffffu); mark(e1 >> 16);
+            const QuadIndices e = decode_quad_indices(ts[off + dsize + kQuadSlotDwords * c], ts[off + dsize + kQuadSlotDwords * c + 1]);
+            for (int v = 0; v < 4; ++v) mark(e.i[v]);
         }
         __syncthreads();
         tot[0] += cnt; tot[1] += n_vol; tot[2] += n_bend;
@@ -128,13 +124,11 @@ __global__ __launch_bounds__(kValidateThreads) void validate_tiles_kernel(const 
         for (int wv = 0; ok && wv < item_waves; ++wv) {
             int barriers = 0;
             for (int st = 0; st < td.n_steps; ++st) {
-                const uint32_t it = ts[td.s_items + (uint32_t)(wv * td.n_steps + st)];
-                const uint32_t type = it & 7u, c = (it >> kItemCountShift) & 127u, o = it >> kItemOffsetShift;
-                if (it & (1u << kItemBarrierBit)) ++barriers;
-                if (type == kItemIdle) continue;
-                const uint32_t bytes4 = type == kItemDistCompact ? c : (type == kItemDistFull ? 2u * c : 4u * c);
-                if (type > kItemBending || td.s_hdr + o + bytes4 > td.s_len) { ok = false; break; }
-                it_tot[type == kItemVolume ? 1 : (type == kItemBending ? 2 : 0)] += c;
+                const WaveItem it = decode_item(ts[td.s_items + (uint32_t)(wv * td.n_steps + st)]);
+                if (it.barrier) ++barriers;
+                if (it.type == kItemIdle) continue;
+                if (it.type > kItemBending || td.s_hdr + it.offset + item_slot_dwords(it.type) * it.count > td.s_len) { ok = false; break; }
+                it_tot[it.type == kItemVolume ? 1 : (it.type == kItemBending ? 2 : 0)] += it.count;
             }
             ok = ok && barriers == td.n_rounds;
         }

@@ -284,7 +284,7 @@ void note_paths(const View &v, const View *unordered, const sbp::Opts &o, const 
         for (int64_t k = 0; k < n_tiles; ++k) {
             const sbk::TileDesc &td = *T.td((size_t)k);
             int nd = 0, nv = 0, nb = 0;
-            for (int r = 0; r < td.n_rounds; ++r) { const uint32_t g = T.words()[td.s_begin + r]; nd += g & 1023u; nv += (g >> 10) & 1023u; nb += (g >> 20) & 1023u; }
+            for (int r = 0; r < td.n_rounds; ++r) { const sbk::GroupWord g = sbk::decode_group_word(T.words()[td.s_begin + r]); nd += (int)g.n_dist; nv += (int)g.n_vol; nb += (int)g.n_bend; }
             if (td.packed_lanes == 128) hit(td.n_pal ? "lane_packed_compact" : "lane_packed_full");
             else if (td.packed_lanes == 256) hit("wide_packed");
             else if (nd) hit(td.n_pal ? "dictionary_slots" : "full_slots");

@@ -33,6 +33,16 @@ def _pair(oracle_mod, mesh, ticks=3, S=7, **kw):
     return x, v
 
 
+def _layer_tile_groups(plan):
+    """Groups of every tile of every T2 layer (phases of kind 3) of a plan."""
+    tasks, groups, out = plan.tasks(), plan.groups(), []
+    for ph in plan.phases():
+        if ph["kind"] == 3:
+            for t in range(ph["task_begin"], ph["task_end"]):
+                out.append(int(np.searchsorted(groups, tasks[t + 1], "left") - np.searchsorted(groups, tasks[t], "left")))
+    return out
+
+
 def test_single_particle_no_constraints(oracle_mod):
     x, v = _pair(oracle_mod, _mesh([[0, 1, 0]], vel=[[1, 0, 0]]))
     assert x[0, 1] < 1.0 and x[0, 0] > 0.0
@@ -79,7 +89,7 @@ def test_ragged_cells_non_cubic_block_and_duplicate_springs(oracle_mod):
         _pair(oracle_mod, m, tile_particles=tile)
 
 
-@pytest.mark.parametrize("cluster_layers", [True, False])
+@pytest.mark.parametrize("cluster_layers", [True, False, "hub_behind_a_small_window"])
 def test_long_range_springs_go_to_cluster_tiles_or_global_colours(oracle_mod, monkeypatch, cluster_layers):
     # springs between random far-apart particles fit no grid cell of any tiling: their connected components become sparse
     # cluster tiles (one T2 layer); with SB_NO_CLUSTER_LAYERS they fall through to the global-colour kernels
@@ -87,7 +97,14 @@ def test_long_range_springs_go_to_cluster_tiles_or_global_colours(oracle_mod, mo
         monkeypatch.setenv("SB_NO_CLUSTER_LAYERS", "1")
     m = jelly_cube(10)
     rng = np.random.default_rng(2)
-    extra = rng.integers(0, m.n, (300, 2)).astype(np.int32)
+    if cluster_layers == "hub_behind_a_small_window":
+        # 950 long springs on ONE particle: the planner spreads them over three T2 layers, and a cluster tile of more than 256 dependent
+        # groups (4 dwords of data each) is longer than the 1 024 dwords the window is set to: the layer's launch (kKindLayer) refills it
+        # while it walks the groups
+        monkeypatch.setenv("SB_WIN_DWORDS", "1024")
+        extra = np.stack([np.zeros(950, np.int64), 1 + rng.choice(m.n - 1, 950, replace=False)], 1).astype(np.int32)
+    else:
+        extra = rng.integers(0, m.n, (300, 2)).astype(np.int32)
     extra = extra[extra[:, 0] != extra[:, 1]]
     m.dist_ij = np.concatenate([m.dist_ij, extra])
     m.dist_rest = np.concatenate([m.dist_rest, np.linalg.norm(m.rest_pos[extra[:, 0]] - m.rest_pos[extra[:, 1]], axis=1).astype(f32)])
@@ -98,6 +115,8 @@ def test_long_range_springs_go_to_cluster_tiles_or_global_colours(oracle_mod, mo
             assert st["n_global_colours"] == 0 and st["t2_constraints"] >= 250
         else:
             assert st["n_global_colours"] > 0
+        if cluster_layers == "hub_behind_a_small_window":
+            assert max(_layer_tile_groups(sb.plan())) > 256
     finally:
         sb.OnDestroy()
     _pair(oracle_mod, m, S=5, tile_particles=64)
@@ -143,6 +162,8 @@ def test_spring_lengths_across_the_float_range(oracle_mod, tile):
     sb = Softbody(m, substeps=2, gravity=(0, 0, 0), tile_particles=tile).Start()
     try:
         o = make_oracle(oracle_mod, m, sb.plan(), gravity=(0, 0, 0))
+        if tile == 512:     # some pairs lie in T2 layers, one group per tile: kKindLayer launches that run the register-resident rounds
+            assert sb.stats()["t2_constraints"] > 0 and max(_layer_tile_groups(sb.plan())) == 1
         x0 = sb.get_positions().copy()
         sb.step(); o.step(0.02, 2)
         x, v = sb.get_positions(), sb.get_velocities()

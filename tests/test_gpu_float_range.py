@@ -4,24 +4,25 @@ zero and infinite), coincident hinge edges, wings on the edge, flat and four tim
 test_spring_lengths_across_the_float_range does for springs. And the state itself subnormal (SPEC.md 1: denormals preserved) through
 integrate, collide and velocity of the tile kernels. tests/test_float_range_oracles.py checks the same inputs on the CPU.
 
-Which form a configuration reaches (no stat tells the wave items from the generic loop; the lines are those of tile_kernel.hip.hpp):
-  items     default                  the branch `QUADS && kTileThreads == 64 * A.item_waves && td.n_steps > 0 && d_hi - d_lo <= win` (line 409):
+Which form a configuration reaches (no stat tells the wave items from the generic loop; the engines are the three branches of
+tile_kernel.hip.hpp titled "engine 1, register-resident rounds", "engine 2, wave items" and "engine 3, windowed group walk"):
+  items     default                  engine 2, wave items (`QUADS && kTileThreads == 64 * A.item_waves && td.n_steps > 0 && d_hi - d_lo <= win`):
                                      project_bending_row for kItemBending, project_volume_quad for kItemVolume; 512-lane workgroups
                                      (schedule.hip launch_tile: quad8)
-  items256  SB_QUAD_LANES=256        the same branch in 4-wave workgroups (item_waves = 4)
-  groups    SB_NO_WAVE_ITEMS=1       no items in the stream (n_steps = 0, item_waves = 0): the `else` of that branch (line 488), its
-                                     `if (QUADS)` part (line 514): project_bending_quad / project_volume_quad by wave slot
+  items256  SB_QUAD_LANES=256        the same engine in 4-wave workgroups (item_waves = 4)
+  groups    SB_NO_WAVE_ITEMS=1       no items in the stream (n_steps = 0, item_waves = 0): engine 3, windowed group walk, its
+                                     `if (QUADS)` part: project_bending_quad / project_volume_quad by wave slot
   window    SB_WIN_DWORDS=1024       the window of every tiling is set to 1024 dwords (tables_host.cpp tiling_limits). The constraints here
                                      are independent, so a workgroup holds a pack of at most 16 four-particle components, 64 dwords of
-                                     slots: every pack fits, the refill at line 507 is NOT taken and the wave items run over another LDS
+                                     slots: every pack fits, the window refill of engine 3 is NOT taken and the wave items run over another LDS
                                      carve. Refills of the generic loop are reached by test_hub_with_tets_and_hinges_walks_more_than_64_steps,
                                      at ordinary scales only.
   global    tile_particles=-1        no tile holds a constraint: global_quad_kernel (aux_kernels.hip.hpp) with the one-lane project_volume /
                                      project_bending, global_distance_kernel for the springs; n_global_colours > 0 says so
 
 The planner cuts space by rest positions, and the scales here differ by 2^84: nearly every constraint is a connected component of its
-own and goes to the T2 layers (KIND 3 of the tile kernel), a few hundred share T0 / T1 tiles around the origin (mixed: springs, tets and
-hinges in one group there). Either way the branch above is the one that projects them.
+own and goes to the T2 layers (kKindLayer of the tile kernel), a few hundred share T0 / T1 tiles around the origin (mixed: springs, tets and
+hinges in one group there). Either way the engine above is the one that projects them.
 """
 import numpy as np
 import pytest

@@ -14,7 +14,8 @@ def _bits(a):
 
 
 @pytest.mark.parametrize("peek_small", [False, True])
-@pytest.mark.parametrize("case", ["hanging_cube", "tets_dragged_over_the_ground", "hanging_cube_global_colours_only"])
+@pytest.mark.parametrize("case", ["hanging_cube", "tets_dragged_over_the_ground", "hanging_cube_global_colours_only", "tets_group_walk",
+                                  "fan_window_refills"])
 def test_moved_pins_match_the_oracle(case, peek_small, oracle_mod, monkeypatch):
     # peek_small: position reads between a move and the step peek (side array + the pending targets scattered onto it) instead of
     # completing the tick, also on these small meshes
@@ -30,11 +31,24 @@ def test_moved_pins_match_the_oracle(case, peek_small, oracle_mod, monkeypatch):
         if case.endswith("global_colours_only"):
             kw["tile_particles"] = -1              # tiles without constraints of their own: the MARK step alone carries the targets
         okw = dict(damping=0.05)
+    elif case == "fan_window_refills":             # one tile of 190 dependent groups behind a 4 KiB window: the fused first kernel refills it
+        from test_gpu_edge_cases import _fan_mesh
+        monkeypatch.setenv("SB_WIN_DWORDS", "1024")
+        mesh = _fan_mesh()
+        pins = np.arange(2, 8, dtype=np.int32)                                                       # six neighbours on the ring
+        kw = dict(substeps=4, distance_compliance=1e-6, volume_compliance=1e-6, bending_compliance=1e-3)
+        okw = dict(compliance=(1e-6, 1e-6, 1e-3))
     else:
-        mesh = bunny_surrogate(target_verts=5000, seed=11)
+        if case == "tets_group_walk":              # no wave items in the stream: the fused first kernel runs the windowed group walk
+            monkeypatch.setenv("SB_NO_WAVE_ITEMS", "1")
+            mesh = bunny_surrogate(target_verts=2000, seed=9)
+        else:
+            mesh = bunny_surrogate(target_verts=5000, seed=11)
         pins = np.argsort(mesh.pos[:, 0])[-40:].astype(np.int32)                                    # a handle on one side
         kw = dict(substeps=6, distance_compliance=1e-7, volume_compliance=1e-7, bending_compliance=1e-4,
                   ground_plane=(0, 1, 0, float(mesh.pos[:, 1].min()) - 0.05))
+        if case == "tets_group_walk":
+            kw["tile_particles"] = 256
         okw = dict(compliance=(1e-7, 1e-7, 1e-4), ground_plane=kw["ground_plane"])
     mesh.inv_mass[pins] = 0.0
     rest = mesh.pos[pins].copy()
@@ -56,7 +70,7 @@ def test_moved_pins_match_the_oracle(case, peek_small, oracle_mod, monkeypatch):
         assert np.array_equal(_bits(x), _bits(o.x)) and np.array_equal(_bits(v), _bits(o.v))
         assert np.array_equal(_bits(x[pins]), _bits(target)) and not v[pins].any()              # where they were put, at rest
         st = sb.stats()
-        # moves that met a held-back last kernel travelled INSIDE the fused first kernel of the next tick (tile_kernel KIND 5)
+        # moves that met a held-back last kernel travelled INSIDE the fused first kernel of the next tick (tile_kernel kKindMidKinematic)
         assert st["ticks_fused_kinematic"] >= (9 if peek_small else 4), st
         assert st["ticks_fused"] >= st["ticks_fused_kinematic"]
         moved = np.linalg.norm(x - mesh.pos, axis=1)
@@ -94,7 +108,7 @@ def test_only_pinned_particles_are_kinematic_and_nothing_changes_on_error():
 def test_target_tables_regrow_while_the_ring_wraps(oracle_mod):
     # Lists of changing length, well past a table's 256-entry floor (the earlier wrap test never leaves it): nine calls wrap the ring of
     # four tables twice -- the slots see 100, 700, 50 / 300, 10 / 650, 400 / 120, 700 targets, so tables are regrown on a later use, and
-    # small lists land in tables grown for large ones -- and a step after every call lets the fused first kernel (tile_kernel KIND 5)
+    # small lists land in tables grown for large ones -- and a step after every call lets the fused first kernel (tile_kernel kKindMidKinematic)
     # read each table in place. The second phase goes round once more without a tick in between.
     mesh = jelly_cube(10)
     pins = np.arange(700, dtype=np.int32)

@@ -2,7 +2,7 @@
 without tets / hinges, with and without ghosts read from the receive buffer) on the smallest meshes that reach it: 2 ticks of 3 substeps,
 positions and velocities bitwise against the oracle. Which shape a case asks for is the rule tests/test_launch_shape.py pins on the CPU;
 a launch at another width than the tables were built for decodes a window that was never staged, i.e. gives other bits.
-(KIND 4 with a descriptor table and KIND 5 run at forced widths in test_gpu_peek.py and test_gpu_kinematic.py.)"""
+(kKindPeek with a descriptor table and kKindMidKinematic run at forced widths in test_gpu_peek.py and test_gpu_kinematic.py.)"""
 import numpy as np
 import pytest
 

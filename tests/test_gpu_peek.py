@@ -1,5 +1,5 @@
 """Position reads between two ticks PEEK instead of completing the tick (include/softbody.h, sb_step / sb_readback_begin):
-tile_kernel<4> runs the held-back last kernel's rounds + collision into a side array and leaves the state alone, so the tick
+tile_kernel<kKindPeek> runs the held-back last kernel's rounds + collision into a side array and leaves the state alone, so the tick
 stays fusable with the next one. What a caller sees must be bit for bit what the flushed path (SB_NO_PEEK=1) and the CPU
 oracle give -- on spring tiles, on tiles with tets and hinges, with particles resting on the ground plane, in the compact
 render-set mode (a subset of the tiles is launched) and with every width of workgroup the launcher picks."""
@@ -59,7 +59,8 @@ def _session(mesh, tri, peek, monkeypatch, ticks, compact, **kw):
         sb.OnDestroy()
 
 
-@pytest.mark.parametrize("case", ["cube_full", "cube_render_set", "cube_heterogeneous_ground", "tets_render_set", "cube_wide_tiles", "cube_large_tiles"])
+@pytest.mark.parametrize("case", ["cube_full", "cube_render_set", "cube_heterogeneous_ground", "tets_render_set", "cube_wide_tiles", "cube_large_tiles",
+                                  "tets_group_walk", "fan_window_refills"])
 def test_peeked_reads_equal_flushed_reads_and_the_oracle(case, monkeypatch, oracle_mod):
     from readback_bench import surface_triangles
     kw, ticks, compact, tri = dict(substeps=6), 5, False, None
@@ -74,6 +75,15 @@ def test_peeked_reads_equal_flushed_reads_and_the_oracle(case, monkeypatch, orac
         mesh = bunny_surrogate(target_verts=6000, seed=7); tri = _surface_triangles_of_tets(mesh); compact = True
         kw = dict(substeps=4, distance_compliance=1e-7, volume_compliance=1e-7, bending_compliance=1e-4,
                   ground_plane=(0, 1, 0, float(mesh.pos[:, 1].min()) + 0.02))
+    elif case == "tets_group_walk":                      # no wave items in the stream: the peek runs the tile kernel's windowed group walk
+        monkeypatch.setenv("SB_NO_WAVE_ITEMS", "1")
+        mesh = bunny_surrogate(target_verts=2000, seed=9); tri = _surface_triangles_of_tets(mesh); compact = True
+        kw = dict(substeps=4, tile_particles=256, distance_compliance=1e-7, volume_compliance=1e-7, bending_compliance=1e-4,
+                  ground_plane=(0, 1, 0, float(mesh.pos[:, 1].min()) + 0.02))
+    elif case == "fan_window_refills":                   # one tile of 190 dependent groups behind a 4 KiB window: the peek refills it
+        from test_gpu_edge_cases import _fan_mesh
+        monkeypatch.setenv("SB_WIN_DWORDS", "1024")
+        mesh = _fan_mesh(); kw = dict(substeps=4, distance_compliance=1e-6, volume_compliance=1e-6, bending_compliance=1e-3)
     elif case == "cube_large_tiles":                     # tiles of up to 1 024 particles: the kernels' second capacity
         mesh = jelly_cube(30); tri = surface_triangles(30); compact = True; kw = dict(substeps=6, tile_particles=1000)
     else:                                                # > 768 tiles: 256-lane workgroups; tile 128 also makes under-full packs

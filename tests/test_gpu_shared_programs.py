@@ -111,7 +111,7 @@ def test_shared_programs_on_hosted_ranks(world, monkeypatch):
 
 
 def test_shared_programs_with_peek_and_kinematic_targets(monkeypatch):
-    # position reads between ticks peek (KIND 4 launches over the tiles' programs), pinned particles move (KIND 5 fused first kernel)
+    # position reads between ticks peek (kKindPeek launches over the tiles' programs), pinned particles move (kKindMidKinematic fused first kernel)
     monkeypatch.setenv("SB_PEEK_MIN_TILES", "0")
     n = 24
     mesh = jelly_cube(n)
