@@ -355,7 +355,9 @@ typedef struct {
      * the tiles' constraint streams, descriptors and particle lists), from the tables actually uploaded -- the model the
      * PMC-measured traffic in profiles/ is checked against (bench.py). Indexed like the slots of sb_step_profiled with
      * G = 0: 0 / 1 = mid-tick kernel on T0 / T1, 2 = first kernel of a tick, 3 = last kernel of a tick (on T0; on T1 it
-     * moves launch_bytes[1] - (launch_bytes[0] - launch_bytes[3])), 4 = all T2 layers of one substep. */
+     * moves launch_bytes[1] - (launch_bytes[0] - launch_bytes[3])), 4 = all T2 layers of one substep. A previous position counts
+     * 12 bytes per read or write, or 8 where the solver hands it from kernel to kernel as a code against x (single-rank spring
+     * lattices on 128-lane launches; the escaped particles' full-width copies are not counted). */
     int64_t launch_bytes[5];
     /* partition (world > 1): how the ownership was made and what it balanced */
     int32_t partition;                              /* SB_PARTITION_BLOCKS or SB_PARTITION_RCB (what AUTO resolved to) */

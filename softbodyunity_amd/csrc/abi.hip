@@ -569,16 +569,17 @@ int sb_get_stats(sb_solver *s, sb_stats *out) {
     out->device_bytes = s->dev_bytes;
     {   // compulsory bytes per launch (see softbody.h): particle state + the tables a launch reads
         const int64_t mb = s->w_uniform ? 0 : (s->w_palette ? 1 : 4);     // inverse mass: nothing (uniform), palette index, or float
+        const int64_t pb = s->prev_codes ? 8 : 12;                        // previous position: coded against x (prev_code.hpp; escapes not counted), or full width
         auto tables = [&](const DevTiling &D) { return D.stream_bytes + (int64_t)D.n_tiles * (int64_t)sizeof(sbk::TileDesc) + (int64_t)D.runs_overflow.count * 8; };
         for (int tl = 0; tl < 2; ++tl) {
             const DevTiling &D = s->tiling[tl];
             if (!D.n_tiles) continue;
-            out->launch_bytes[tl] = D.staged_particles * (12 + mb + 12 + 12 + 12) + tables(D);   // x, w, xprev in; x, xprev out
+            out->launch_bytes[tl] = D.staged_particles * (12 + mb + pb + 12 + pb) + tables(D);   // x, w, xprev in; x, xprev out
         }
         const DevTiling &D0 = s->tiling[0];
         if (D0.n_tiles) {
-            out->launch_bytes[2] = D0.staged_particles * (12 + mb + 12 + 12 + 12) + tables(D0);  // x, w, v in; x, xprev out
-            out->launch_bytes[3] = D0.staged_particles * (12 + mb + 12 + 12 + 12) + tables(D0);  // x, w, xprev in; x, v out
+            out->launch_bytes[2] = D0.staged_particles * (12 + mb + 12 + 12 + pb) + tables(D0);  // x, w, v in; x, xprev out
+            out->launch_bytes[3] = D0.staged_particles * (12 + mb + pb + 12 + 12) + tables(D0);  // x, w, xprev in; x, v out
         }
         const DevTiling &D2 = s->tiling[2];
         if (D2.n_tiles) out->launch_bytes[4] = D2.staged_particles * (4 + 12 + mb + 12) + tables(D2);

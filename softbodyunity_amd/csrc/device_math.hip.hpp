@@ -27,6 +27,11 @@ __device__ __forceinline__ void store3_through(float *p, float x, float y, float
     f32x3_t v = {x, y, z};
     asm volatile("global_store_dwordx3 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
 }
+// the same for the 8 bytes of a previous-position code (prev_code.hpp)
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store2_through(uint2 *p, u32x2_t v) {
+    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+}
 
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 sub3(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }

@@ -36,6 +36,7 @@ constexpr bool kind_rounds_before_mark(int k) { return k != kKindFirst; }       
 constexpr bool kind_rounds_after_mark(int k) { return k == kKindFirst || kind_base(k) == kKindMid; }
 constexpr bool kind_ends_tick(int k) { return k == kKindLast || k == kKindPeek; }                               // MARK stops at the collided positions
 constexpr bool kind_reads_prev(int k) { return kind_base(k) == kKindMid || k == kKindLast; }                    // v = (x - xprev) / h
+constexpr bool kind_touches_prev(int k) { return k == kKindFirst || kind_reads_prev(k); }                       // writes or reads previous positions: the kinds with a CODED build
 constexpr bool kind_writes_peek(int k) { return k == kKindPeek; }                                               // else: the state arrays
 constexpr bool kind_may_read_ghosts(int k) { return k == kKindMid || k == kKindLast; }                          // T1 launches of a lattice-type plan
 constexpr bool kind_gathers(int k) { return k == kKindLayer; }                                                  // particles from the gather list, not from runs
@@ -106,7 +107,12 @@ struct TileArgs {
     // GHOSTS kernels (world > 1, T1 launches of a lattice-type plan): particle g >= n_owned is ghost g - n_owned and its position
     // and previous position are read straight from the receive buffer of the exchange that just ended (6 floats per ghost, in
     // ghost order) instead of from the arrays -- the unpack kernel between the exchange and this launch is gone
-    const float *ghost_src;
+    // CODED kernels (world 1, no ghosts; prev_code.hpp): one 8-byte code per local particle instead of `prev`, which then holds only the
+    // escaped particles' previous positions. The two never meet in one kernel and share the slot, so the argument block keeps its layout.
+    union {
+        const float *ghost_src;
+        uint2 *prev_code;
+    };
     int32_t n_owned;
     // kKindPeek: where the tick-end positions of the launch's tiles go (packed xyz, device numbering); the state arrays stay as
     // they are

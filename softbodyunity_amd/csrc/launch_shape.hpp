@@ -40,4 +40,31 @@ inline LaunchShape tile_launch_shape(const TilingScalars &D, int tile_lanes, int
     return sh;
 }
 
+// ---- previous positions as 8-byte codes (prev_code.hpp) ---------------------------------------------------------------------------------
+// Decided once per solver (sb_finalize), not per launch: a code is written by one tile kernel and read by the next, so either every tile
+// launch of the tick runs a coded kernel or none does. The coded kernels are built for 128 x 4 spring-only launches with palette masses.
+// every launch of the tiling is 128 x 4 without quads, whatever its number of tiles (the tiling-level part of `narrow` above; wide8 is off then)
+inline bool tiling_always_narrow(const TilingScalars &D, int tile_lanes) {
+    if (D.n_tiles == 0) return true;       // (a plan with one tiling: the other one is never launched)
+    return D.max_local <= sbk::kSmallTile && !D.has_quads && (D.packed_lanes ? D.packed_lanes == sbk::kLanePackLanes : tile_lanes == sbk::kNarrowTileThreads);
+}
+// The 512^3 check of tests/test_gpu_full_size.py holds sb_stats.launch_bytes of that lattice to the full-width format (> 7e9 B per launch); until
+// that figure is recorded anew, lattices beyond this many local particles keep the full-width path. No property of the code sets the limit.
+constexpr int64_t kPrevCodeMaxParticles = (int64_t)1 << 26;
+struct PrevCodeInputs {
+    int world = 1;
+    int halo_slots = 0;              // active halo slots (a loopback solver has world 1 and halo slots)
+    int tile_lanes = 0;              // sb_solver's tuning field
+    bool w_palette = false;          // the kernels read palette masses (WPAL)
+    int steps_between_tiles = 0;     // T2 layers + global colours: they move x between two tile kernels, and a code is relative to the x stored beside it
+    int64_t n_local = 0;
+};
+inline bool use_prev_codes(const TilingScalars &T0, const TilingScalars &T1, const PrevCodeInputs &in) {
+    if (in.world != 1 || in.halo_slots != 0) return false;                    // ghosts, halo pack / unpack and peer push read full-width previous positions
+    if (!in.w_palette) return false;                                          // the float-mass kernels have no registers left for it
+    if (in.steps_between_tiles != 0) return false;
+    if (T0.n_tiles == 0 || in.n_local > kPrevCodeMaxParticles) return false;
+    return tiling_always_narrow(T0, in.tile_lanes) && tiling_always_narrow(T1, in.tile_lanes);
+}
+
 }  // namespace sbt

@@ -205,9 +205,9 @@ void halo_exchange(sb_solver *s, int slot, hipStream_t st) {
 }
 
 // The one place that launches tile_kernel: the block size IS the kernel's THREADS.
-template <int KIND, bool Q, int THREADS, int PPT, bool W, int G>
+template <int KIND, bool Q, int THREADS, int PPT, bool W, int G, bool C = false>
 void launch_tile_kernel(const sb_solver *s, const DevTiling &D, const sbk::TileDesc *tiles_at_base, int n_wg, const sbk::TileArgs &A) {
-    hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, THREADS, PPT, W, G>), dim3(n_wg), dim3(THREADS), D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);
+    hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, THREADS, PPT, W, G, C>), dim3(n_wg), dim3(THREADS), D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);
 }
 // From the shape (launch_shape.hpp) to the instantiation. 512 x 2 is built for tiles with tets / hinges only; a shape without a kernel is an error.
 template <int KIND, bool Q, bool W, int G>
@@ -247,6 +247,14 @@ void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = 
     constexpr bool kCanGhost = sbk::kind_may_read_ghosts(KIND);
     if (ghosts && !(kCanGhost && !D.has_quads)) throw std::runtime_error("internal: ghost-reading tile kernel requested for a launch that has none");
     const bool W = s->w_palette;
+    // A solver with 8-byte previous-position codes (decided at sb_finalize, launch_shape.hpp use_prev_codes) runs the coded build of every
+    // kernel that writes or reads them; the rule there guarantees the one shape they are built for. Anything else is an error, never a
+    // quiet full-width launch: the neighbouring launches would read codes that were not written.
+    if constexpr (sbk::kind_touches_prev(KIND)) if (s->prev_codes) {
+        if (ghosts || sh.quads || !W || !sbt::same_width(sh, sbt::kShapeNarrow)) throw std::runtime_error("internal: previous-position codes are on, but the launch is not 128 x 4 spring-only with palette masses");
+        A.prev_code = s->d_prev_code.p;
+        return launch_tile_kernel<KIND, false, sbt::kShapeNarrow.threads, sbt::kShapeNarrow.ppt, true, sbk::kHaloNone, true>(s, D, tiles_at_base, n_wg, A);
+    }
     if (ghosts) {
         if constexpr (kCanGhost) W ? launch_tile_shaped<KIND, false, true, sbk::kHaloGhosts>(s, D, sh, tiles_at_base, n_wg, A) : launch_tile_shaped<KIND, false, false, sbk::kHaloGhosts>(s, D, sh, tiles_at_base, n_wg, A);
     } else if (sh.quads) W ? launch_tile_shaped<KIND, true, true, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A) : launch_tile_shaped<KIND, true, false, sbk::kHaloNone>(s, D, sh, tiles_at_base, n_wg, A);

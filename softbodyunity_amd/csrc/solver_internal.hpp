@@ -185,6 +185,10 @@ struct sb_solver {
     bool w_uniform = false;          // one distinct inverse mass: the tile kernels skip the per-particle index read
     sbk::PosView pos_view() const { return sbk::PosView{d_pos3.p, d_wf.p}; }
     DevBuf<float> d_prev, d_vel;
+    // Previous positions as 8-byte codes against x (prev_code.hpp), decided once at sb_finalize (launch_shape.hpp use_prev_codes): the tile
+    // kernels then hand d_prev_code to each other and d_prev holds only the particles whose code does not fit. Nothing else reads either.
+    bool prev_codes = false;
+    DevBuf<uint2> d_prev_code;       // one per local particle
     DevBuf<sbk::TickParams> d_tp;
     DevBuf<float> d_sendbuf, d_recvbuf;   // 3 (slot 1: 6) floats per ghost, peers back to back
     DevTiling tiling[3];             // T0, T1, and the sparse T2 tiles (all layers; see t2_layer_range)

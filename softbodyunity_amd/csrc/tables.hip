@@ -4,6 +4,7 @@
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree); the exported functions are the
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
 #include "solver_internal.hpp"
+#include "launch_shape.hpp"
 
 namespace sbi {
 
@@ -158,6 +159,17 @@ void build_device(sb_solver *s) {
     if (H.recv_floats) HIP_CHECK(hipMemset(s->d_recvbuf.p, 0, H.recv_floats * sizeof(float)));
     s->fused_unpack = H.fused_unpack;
     if (s->peer.enabled && L.world > 1) alloc_mailbox(s, H.mailbox);
+    // previous positions as 8-byte codes between the tile kernels: for the whole solver or not at all (launch_shape.hpp)
+    sbt::PrevCodeInputs pc;
+    pc.world = s->desc.world; pc.tile_lanes = s->tile_lanes; pc.w_palette = s->w_palette; pc.n_local = s->n_local;
+    pc.halo_slots = s->loopback ? 1 : 0;
+    for (const auto &D : s->halos) if (D->active()) ++pc.halo_slots;
+    pc.steps_between_tiles = (int)s->t2_layer_range.size() + (int)s->gcolours.size();
+    s->prev_codes = sbt::use_prev_codes(s->tiling[0], s->tiling[1], pc);
+    if (s->prev_codes) {
+        s->d_prev_code.alloc((size_t)s->n_local, s->dev_bytes);
+        HIP_CHECK(hipMemset(s->d_prev_code.p, 0, (size_t)s->n_local * sizeof(uint2)));
+    }
 }
 
 }  // namespace sbi

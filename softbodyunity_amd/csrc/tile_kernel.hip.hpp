@@ -3,6 +3,7 @@
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 #pragma once
 #include "device_math.hip.hpp"
+#include "prev_code.hpp"
 
 namespace sbk {
 
@@ -37,7 +38,11 @@ __device__ __forceinline__ void quad_slot_offsets(const uint4 &e, int q, int &o0
 // Register budget (HIP: second launch-bound = waves per SIMD). LDS allows ~14 tiles per CU, so aim for that many waves.
 template <bool QUADS, int THREADS> constexpr int kWavesPerSimd = QUADS ? (THREADS == 64 ? 3 : (THREADS == 512 ? 2 : 4)) : (THREADS == 256 ? 8 : (THREADS == 128 ? 6 : 4));   // 128 lanes: 7 waves (72 VGPRs) measured 1 % slower, 8 spill
 // WPAL = inverse masses are read as one-byte palette indices (the palette entry comes from another lane by ds_bpermute).
-template <int KIND_, bool QUADS, int THREADS, int PPT, bool WPAL, int HALO = kHaloNone>
+// CODED = previous positions travel between the tile kernels of a tick as 8-byte codes against x (prev_code.hpp): the prologue decodes
+// them once x has arrived, MARK keeps the new previous position in the registers of the old one, the final store encodes it against the x
+// it writes. A particle whose code does not fit sets the escape bit and uses A.prev as before. The first kernel only writes codes, the last
+// one only reads them; the host launches either coded kernels in every tile launch of a solver or in none (launch_shape.hpp use_prev_codes).
+template <int KIND_, bool QUADS, int THREADS, int PPT, bool WPAL, int HALO = kHaloNone, bool CODED = false>
 // (kKindMidKinematic -- one launch per tick, and only when kinematic targets are pending -- gets one wave per SIMD less: its MARK step holds more
 // live values, and under the ordinary bound it spilled 4 .. 14 registers)
 __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ == 5 && !QUADS ? 1 : 0))) void tile_kernel(const TileDesc *tiles_at_base, int n_workgroups, TileArgs A) {
@@ -147,6 +152,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     f32x4 X[PPT];
     float pvx[PPT], pvy[PPT], pvz[PPT];
     uint32_t wi[PPT];
+    uint32_t pc_lo[PPT], pc_hi[PPT];      // CODED: the particle's code as loaded
     const int mypal = WPAL ? __float_as_int(A.wpal[tid & (kMaxMassPalette - 1)]) : 0;   // lane l holds palette entry l
 #pragma unroll
     for (int m = 0; m < PPT; ++m) {
@@ -157,9 +163,13 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
         X[m].x = px[0]; X[m].y = px[1]; X[m].z = px[2];
         if (WPAL) { wi[m] = A.w8[A.w_uniform ? 0 : gc]; X[m].w = 0.0f; } else { wi[m] = 0; X[m].w = A.pos.w[gc]; }
         pvx[m] = pvy[m] = pvz[m] = 0.0f;
+        pc_lo[m] = pc_hi[m] = 0u;
         if (kind_reads_prev(KIND_)) {
-            const float *pp = ghost ? px + 3 : A.prev + 3 * (size_t)gc;
-            pvx[m] = pp[0]; pvy[m] = pp[1]; pvz[m] = pp[2];
+            if (CODED) { const uint2 c = A.prev_code[gc]; pc_lo[m] = c.x; pc_hi[m] = c.y; }
+            else {
+                const float *pp = ghost ? px + 3 : A.prev + 3 * (size_t)gc;
+                pvx[m] = pp[0]; pvy[m] = pp[1]; pvz[m] = pp[2];
+            }
         }
     }
     const bool rounds_in_lds = n_rounds_all <= A.rounds_dwords;
@@ -211,8 +221,30 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     // One common use of every loaded value: the scheduler cannot sink a load below it, so all loads are issued
     // first and a single wait follows (left alone it emits load, wait, LDS write, load, wait, ... to save registers).
 #pragma unroll
-    for (int m = 0; m < PPT; ++m) asm volatile("" ::"v"(X[m].x), "v"(pvx[m]), "v"(wi[m]), "v"(X[m].w));
+    for (int m = 0; m < PPT; ++m) {
+        if (CODED) asm volatile("" ::"v"(X[m].x), "v"(pc_lo[m]), "v"(wi[m]), "v"(X[m].w));
+        else asm volatile("" ::"v"(X[m].x), "v"(pvx[m]), "v"(wi[m]), "v"(X[m].w));
+    }
     asm volatile("" ::"v"(mypal));
+    if (CODED && kind_reads_prev(KIND_)) {
+        // x is here: decode. An escaped particle's previous position comes from the full-width array, one more dependent load, behind a
+        // wave-uniform test (most waves hold no escape at all); its wait falls in front of MARK, behind the first pass of rounds.
+        bool esc = false;
+#pragma unroll
+        for (int m = 0; m < PPT; ++m) {
+            const Bits3 p = prev_decode((uint64_t)pc_lo[m] | ((uint64_t)pc_hi[m] << 32), Bits3{__float_as_uint(X[m].x), __float_as_uint(X[m].y), __float_as_uint(X[m].z)});
+            pvx[m] = __uint_as_float(p.x); pvy[m] = __uint_as_float(p.y); pvz[m] = __uint_as_float(p.z);
+            esc = esc || (g[m] >= 0 && prev_hi_is_escape(pc_hi[m]));
+        }
+        if (__builtin_amdgcn_ballot_w64(esc) != 0ull) {
+#pragma unroll
+            for (int m = 0; m < PPT; ++m)
+                if (g[m] >= 0 && prev_hi_is_escape(pc_hi[m])) {
+                    const float *pp = A.prev + 3 * (size_t)g[m];
+                    pvx[m] = pp[0]; pvy[m] = pp[1]; pvz[m] = pp[2];
+                }
+        }
+    }
     if (WPAL) {
 #pragma unroll
         for (int m = 0; m < PPT; ++m) X[m].w = __int_as_float(__builtin_amdgcn_ds_bpermute((int)(wi[m] << 2), mypal));
@@ -287,7 +319,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                 if (KIND == kKindLast) {
                     A.vel[o + 0] = vx; A.vel[o + 1] = vy; A.vel[o + 2] = vz;
                 } else {
-                    if (A.store_through & 1) store3_through(A.prev + o, P.x, P.y, P.z);
+                    if (CODED) { pvx[m] = P.x; pvy[m] = P.y; pvz[m] = P.z; }      // (written out, coded, by the final store)
+                    else if (A.store_through & 1) store3_through(A.prev + o, P.x, P.y, P.z);
                     else { A.prev[o + 0] = P.x; A.prev[o + 1] = P.y; A.prev[o + 2] = P.z; }
                     if (P.w > 0.0f) {
                         vx = vx + tp.hgx; vy = vy + tp.hgy; vz = vz + tp.hgz;
@@ -632,6 +665,18 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             if (kind_writes_peek(KIND_)) { float *o = A.peek_out + 3 * (size_t)g[m]; o[0] = P.x; o[1] = P.y; o[2] = P.z; }
             else if (A.store_through & 2) store3_through(A.pos.xyz + 3 * (size_t)g[m], P.x, P.y, P.z);
             else pv_store(A.pos, g[m], P);
+            if (CODED && kind_has_mark(KIND_) && !kind_ends_tick(KIND_)) {
+                // the previous position MARK left in registers, against the x just stored; what does not fit goes out at full width
+                const PrevCode e = prev_encode(Bits3{__float_as_uint(pvx[m]), __float_as_uint(pvy[m]), __float_as_uint(pvz[m])}, Bits3{__float_as_uint(P.x), __float_as_uint(P.y), __float_as_uint(P.z)});
+                const u32x2_t c = {(uint32_t)e.code, (uint32_t)(e.code >> 32)};
+                if (A.store_through & 1) store2_through(A.prev_code + g[m], c);
+                else *reinterpret_cast<u32x2_t *>(A.prev_code + g[m]) = c;
+                if (!e.fits) {
+                    float *o = A.prev + 3 * (size_t)g[m];
+                    if (A.store_through & 1) store3_through(o, pvx[m], pvy[m], pvz[m]);
+                    else { o[0] = pvx[m]; o[1] = pvy[m]; o[2] = pvz[m]; }
+                }
+            }
         }
 }
 
