@@ -4,6 +4,7 @@
 // FixedUpdate() -> sb_group_step(Time.fixedDeltaTime, substeps) + sb_group_get_positions                     (one tick, SPEC.md §2)
 //                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
 //                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
+// Teleport() / Respawn() -> sb_group_place: the body follows a requested position and rotation, or starts over from its rest pose (SPEC.md 2d)
 // OnDestroy()   -> sb_group_destroy
 //
 // A Unity player is ONE process: the component talks to the plugin through include/softbody_group.h, where `deviceCount` GPUs sit
@@ -464,6 +465,59 @@ namespace SoftbodyMI355X
             bodyHas = 0;
             if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_impulses(handle, impulseQueue, count), "sb_group_apply_impulses");
             else if (cpu != null) cpu.ApplyImpulses(impulseQueue, count, renderTriangles);
+        }
+
+        /// <summary>transform.position / rotation = ... (Rigidbody.MovePosition + MoveRotation) for the soft body, between two ticks and on the GPUs
+        /// (SPEC.md 2d, sb_group_place): one POSE query for the mass centre and the best-fit rotation, then ONE rigid map that carries that
+        /// frame onto the requested one -- the mass centre lands on `position`, bodyRotation becomes `rotation`, the deformation and the
+        /// motion are kept (velocities turn with the body). Pinned particles move along. World space. Impulses queued so far are sent first.</summary>
+        public void Teleport(Vector3 position, Quaternion rotation)
+        {
+            SendImpulses();
+            SbBodyState s = QueryBody(SoftbodyNative.BodyPose);
+            var have = new Quaternion((float)s.rotationX, (float)s.rotationY, (float)s.rotationZ, (float)s.rotationW);
+            Quaternion turn = (Quaternion.Inverse(FrameRotation()) * rotation) * Quaternion.Inverse(have);
+            Place(0u, turn, new Vector3((float)s.comX, (float)s.comY, (float)s.comZ), WorldToSimPoint(position), Vector3.zero, Vector3.zero);
+        }
+
+        /// <summary>Respawn: the body back in its reference pose -- undeformed --, its mass centre at `position`, turned by `rotation`, moving with
+        /// `velocity` and spinning with `angularVelocity` (radians per second) about that point; the defaults leave it at rest (SPEC.md 2d,
+        /// SB_PLACE_FROM_REFERENCE). World space. Pinned particles are respawned with the body and keep their (zero) velocities.</summary>
+        public void Respawn(Vector3 position, Quaternion rotation, Vector3 velocity = default(Vector3), Vector3 angularVelocity = default(Vector3))
+        {
+            SendImpulses();
+            SbBodyState s = QueryBody(SoftbodyNative.BodyPose);      // (for refCom: the mass centre of the reference pose)
+            Quaternion toSim = Quaternion.Inverse(FrameRotation());
+            Place(SoftbodyNative.SB_PLACE_FROM_REFERENCE, toSim * rotation, new Vector3((float)s.refComX, (float)s.refComY, (float)s.refComZ), WorldToSimPoint(position),
+                  WorldToSimVector(velocity), toSim * angularVelocity);
+        }
+
+        Quaternion FrameRotation() => transformFollowsBody ? simRotation : transform.rotation;
+
+        /// <summary>x' = R (src - from) + to in simulation space: sb_group_place, or -- CPU branch -- the same section 2d on the arrays the C# solver steps.</summary>
+        void Place(uint flags, Quaternion r, Vector3 from, Vector3 to, Vector3 lin, Vector3 ang)
+        {
+            Matrix4x4 m = Matrix4x4.Rotate(r);
+            bodyHas = 0;
+            if (handle != IntPtr.Zero)
+            {
+                var p = new SbPlacement { flags = flags, m00 = m.m00, m01 = m.m01, m02 = m.m02, m10 = m.m10, m11 = m.m11, m12 = m.m12, m20 = m.m20, m21 = m.m21, m22 = m.m22,
+                                          fromX = from.x, fromY = from.y, fromZ = from.z, toX = to.x, toY = to.y, toZ = to.z,
+                                          linX = lin.x, linY = lin.y, linZ = lin.z, angX = ang.x, angY = ang.y, angZ = ang.z };
+                SoftbodyNative.Check(SoftbodyNative.sb_group_place(handle, ref p), "sb_group_place");
+                return;
+            }
+            bool fromReference = (flags & SoftbodyNative.SB_PLACE_FROM_REFERENCE) != 0;
+            bool setVelocity = fromReference || (flags & SoftbodyNative.SB_PLACE_SET_VELOCITY) != 0;
+            Vector3[] src = fromReference ? (restPositions ?? positions) : positions;
+            for (int i = 0; i < positions.Length; ++i)
+            {
+                if ((flags & SoftbodyNative.SB_PLACE_KEEP_PINNED) != 0 && inverseMass[i] == 0f) continue;
+                Vector3 x = m.MultiplyVector(src[i] - from) + to;
+                positions[i] = x;
+                if (!(inverseMass[i] > 0f)) continue;
+                velocities[i] = setVelocity ? lin + Vector3.Cross(ang, x - to) : m.MultiplyVector(velocities[i]);
+            }
         }
 
         /// <summary>Attachments: move pinned particles (inverse mass 0) to new positions before the next FixedUpdate; their constrained

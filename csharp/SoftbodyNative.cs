@@ -160,6 +160,20 @@ namespace SoftbodyMI355X
         public double kineticEnergy;
     }
 
+    /// <summary>sb_placement (92 bytes): what sb_group_place takes (SPEC.md 2d). x' = m (src - from) + to, m row-major, src the positions or -- under
+    /// SB_PLACE_FROM_REFERENCE -- the reference pose; velocities turn with m, or become lin + ang x (x' - to) under SB_PLACE_SET_VELOCITY and always
+    /// under SB_PLACE_FROM_REFERENCE; SB_PLACE_KEEP_PINNED leaves pinned particles alone. reserved stays 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbPlacement
+    {
+        public uint flags, reserved;
+        public float m00, m01, m02, m10, m11, m12, m20, m21, m22;
+        public float fromX, fromY, fromZ;
+        public float toX, toY, toZ;
+        public float linX, linY, linZ;
+        public float angX, angY, angZ;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -186,6 +200,9 @@ namespace SoftbodyMI355X
         // sb_impulse (SPEC.md 2c), named as in include/softbody.h
         public const int SB_IMPULSE_PARTICLE = 0, SB_IMPULSE_SURFACE = 1, SB_IMPULSE_RADIAL = 2;      // SbImpulse.kind
         public const uint SB_IMPULSE_VELOCITY_CHANGE = 1, SB_IMPULSE_LINEAR_FALLOFF = 2;               // SbImpulse.flags (LINEAR_FALLOFF: RADIAL only)
+
+        // sb_placement.flags (SPEC.md 2d), named as in include/softbody_group.h
+        public const uint SB_PLACE_FROM_REFERENCE = 1, SB_PLACE_SET_VELOCITY = 2, SB_PLACE_KEEP_PINNED = 4;
 
         [DllImport(Lib, CallingConvention = CC)] public static extern void sb_desc_default(ref SbDesc d);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_create(ref SbDesc desc, out IntPtr solver);
@@ -290,6 +307,7 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_raycast(IntPtr g, float[] rays, int count, [Out] SbRayHit[] hits);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_place(IntPtr g, ref SbPlacement placement);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);

@@ -163,6 +163,31 @@ int sb_group_get_body_state(sb_group *g, uint32_t what, sb_body_state *out);
  * does not cover are ignored. SB_ERR_INVALID_ARG as above, or for a negative count. */
 int sb_group_body_state_from_sums(const double sums[32], int64_t n_dynamic, int64_t n_pinned, uint32_t what, sb_body_state *out);
 
+/* ---- placement: move, rotate, respawn between two ticks (SPEC.md 2d) --------------------------------------------------------------------- */
+/* What transform.position = ..., Rigidbody.MovePosition / MoveRotation and a respawn are to a rigid body: ONE affine map over positions and
+ * velocities of the whole body, on the devices -- one streaming pass per rank over every particle it holds, ghosts included (the same
+ * arithmetic on a ghost gives its owner's bits: no exchange) -- instead of sb_group_get_positions + sb_group_get_velocities + a host loop +
+ * sb_group_set_state. Per particle, in binary32 without FMA (SPEC.md 2d has the parentheses):
+ *     x' = m (src - from) + to,   src = x, or the reference pose q (SPEC.md 6f) under SB_PLACE_FROM_REFERENCE
+ *     v' = m v                    for inverse mass > 0 (a rotated body keeps flying, rotated), or
+ *     v' = lin + ang x (x' - to)  under SB_PLACE_SET_VELOCITY and always under SB_PLACE_FROM_REFERENCE (lin = ang = 0: at rest)
+ * A pinned particle moves with the body (no spring to a pin is stretched) and keeps its velocity's bits; SB_PLACE_KEEP_PINNED leaves it
+ * entirely alone (a body hanging from a world anchor). m is any finite row-major 3x3 matrix; rest lengths do not scale with it. A written
+ * component that comes out NaN is stored as 0x7fc00000. Asynchronous; completes every rank's held-back last kernel first, as
+ * sb_group_apply_impulses does, which lands pending kinematic targets (old frame) before they are mapped like every other position. The
+ * ground plane, the render snapshot delivered last and the render device take no part. */
+#define SB_PLACE_FROM_REFERENCE 1u
+#define SB_PLACE_SET_VELOCITY   2u
+#define SB_PLACE_KEEP_PINNED    4u
+typedef struct {
+    uint32_t flags, reserved;      /* SB_PLACE_*; reserved = 0 */
+    float m[9], from[3], to[3], lin[3], ang[3];
+} sb_placement;                    /* 92 bytes */
+/* SB_ERR_INVALID_ARG (null argument, unknown flag bit, reserved != 0, a NaN or infinite field: all checked before the group is touched),
+ * SB_ERR_STATE before sb_group_finalize; a refused call changes nothing. The first SB_PLACE_FROM_REFERENCE call uploads the reference pose
+ * of every particle a rank holds (12 bytes each); until then sb_stats.device_bytes is what it was. Both host models. */
+int sb_group_place(sb_group *g, const sb_placement *p);
+
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);
 int32_t sb_group_rank_count(const sb_group *g);

@@ -476,6 +476,10 @@ int finalize_link(sb_solver *s) {
             s->ref_pose.resize((size_t)s->n_owned * 3);
             for (int64_t l = 0; l < s->n_owned; ++l)
                 for (int c = 0; c < 3; ++c) s->ref_pose[3 * (size_t)l + c] = rp[3 * (size_t)l2o[(size_t)l] + c];
+            // ... and of the ghosts behind them (a window's authored rest positions cover its ghosts): what SB_PLACE_FROM_REFERENCE needs besides
+            s->ref_pose_ghost.resize((size_t)(s->n_local - s->n_owned) * 3);
+            for (int64_t l = s->n_owned; l < s->n_local; ++l)
+                for (int c = 0; c < 3; ++c) s->ref_pose_ghost[3 * (size_t)(l - s->n_owned) + c] = rp[3 * (size_t)l2o[(size_t)l] + c];
         }
         // the authored arrays are no longer needed: dropped in place, or -- the whole mesh a group's ranks share, the group still holding
         // it -- left to the others, with this rank's own copy of what is read after finalize

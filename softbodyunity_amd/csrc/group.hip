@@ -555,6 +555,17 @@ int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count)
     });
 }
 
+int sb_group_place(sb_group *g, const sb_placement *p) {
+    // null and struct checks before the group is touched: refused the same way on a machine without a device
+    if (!g || !p) return fail(SB_ERR_INVALID_ARG, "sb_group_place: null argument");
+    if (int rc = validate_placement("sb_group_place", p)) return rc;
+    if (int rc = check_group(g, true, "sb_group_place")) return rc;
+    // the same struct to every rank: each maps what it holds, ghosts included, and completes its tick (an identity map too: the ranks
+    // stay in the same tick state). The render device takes no part.
+    const sb_placement P = *p;
+    return g->for_ranks([&](int r) { return guarded([&]() -> int { return place_validated(g->ranks[(size_t)r], P); }); });
+}
+
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */
 
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {

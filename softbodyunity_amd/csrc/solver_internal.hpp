@@ -3,7 +3,7 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), stream_codec.hpp (the bit layout of the tile constraint stream: the builder's encoders, the kernels' and the validator's decoders), tables.hip (their upload), launch_shape.hpp (which tile_kernel
-// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), render.hip (render readback: the stage and the entry-point bodies a solver
+// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), placement.hip (placement between two ticks: one affine map over the whole body), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
 // window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
@@ -298,6 +298,10 @@ struct sb_solver {
     DevBuf<float> d_ref_pose;
     DevBuf<double> d_body_partials;
     sbi::HostBuf<double> h_body;
+    // Placement (sb_group_place, placement.hip; SPEC.md 2d): SB_PLACE_FROM_REFERENCE reads the reference pose of EVERY local particle. The
+    // ghosts' part is kept on the host by sb_finalize beside ref_pose (12 bytes per ghost); the first such call puts both on the device
+    DevBuf<float> d_place_ref;             // packed xyz per local particle, device order
+    std::vector<float> ref_pose_ghost;
 
     // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
     // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
@@ -370,6 +374,10 @@ int64_t impulse_triangles_in_force(const RenderState &R);       // triangles of 
 int validate_impulses(const char *who, const sb_impulse *items, int32_t count, int32_t n, int64_t m_tri, bool rank);
 void expand_impulses(const RenderState &R, const sb_impulse *items, int32_t count, std::vector<sb_impulse> &out);      // SURFACE -> PARTICLE-like entries
 int apply_impulses_validated(sb_solver *s, const sb_impulse *items, int32_t count);      // PARTICLE / RADIAL, the rank's numbering, owned particles
+
+// ---- placement.hip: placement between two ticks (SPEC.md 2d) -------------------------------------------------------------------------------
+int validate_placement(const char *who, const sb_placement *p);      // the struct alone: needs neither a group nor a device
+int place_validated(sb_solver *s, const sb_placement &p);            // every local particle, ghosts included; asynchronous on s->stream
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

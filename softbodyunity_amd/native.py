@@ -33,6 +33,7 @@ SB_IMPULSE_PARTICLE, SB_IMPULSE_SURFACE, SB_IMPULSE_RADIAL = 0, 1, 2
 SB_IMPULSE_VELOCITY_CHANGE, SB_IMPULSE_LINEAR_FALLOFF = 1, 2
 SB_BODY_POSE, SB_BODY_MOTION = 1, 2
 SB_BODY_NO_MASS, SB_BODY_DEGENERATE_POSE, SB_BODY_DEGENERATE_INERTIA = 1, 2, 4
+SB_PLACE_FROM_REFERENCE, SB_PLACE_SET_VELOCITY, SB_PLACE_KEEP_PINNED = 1, 2, 4
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -129,6 +130,12 @@ class SbBodyState(C.Structure):
             out[name] = np.array(v[:], np.float64) if hasattr(v, "__len__") else v
         out["apq"] = out["apq"].reshape(3, 3)
         return out
+
+
+class SbPlacement(C.Structure):
+    """sb_placement (92 bytes): what sb_group_place takes (SPEC.md 2d). m row-major; flags = SB_PLACE_*; `frm` is the header's `from`"""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("m", C.c_float * 9), ("frm", C.c_float * 3), ("to", C.c_float * 3),
+                ("lin", C.c_float * 3), ("ang", C.c_float * 3)]
 
 
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
@@ -235,6 +242,7 @@ SIGNATURES = {
     "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
+    "sb_group_place": (C.c_int, [_P, C.POINTER(SbPlacement)]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),

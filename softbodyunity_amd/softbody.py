@@ -396,6 +396,30 @@ def _apply_impulses(fn, handle, items):
     check(fn(handle, items.ctypes.data_as(C.POINTER(native.SbImpulse)), int(items.shape[0])))
 
 
+def placement_from_rotation(quat_xyzw, scale=1.0):
+    """-> the (3, 3) float32 matrix SoftbodyGroup.place takes as m: the rotation of a quaternion (x, y, z, w) -- normalised here, computed in
+    binary64 and rounded once -- times a uniform scale (rest lengths do not scale: a scaled body is squashed and recovers)."""
+    q = np.asarray(quat_xyzw, np.float64).reshape(4)
+    x, y, z, w = q / np.sqrt(np.dot(q, q))
+    m = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+    return (float(scale) * m).astype(np.float32)
+
+
+def make_placement(m=None, frm=(0, 0, 0), to=(0, 0, 0), lin=None, ang=None, from_reference=False, keep_pinned=False):
+    """-> native.SbPlacement (SPEC.md 2d): x' = m (src - frm) + to. lin / ang given: SB_PLACE_SET_VELOCITY (v' = lin + ang x (x' - to))."""
+    p = native.SbPlacement()
+    p.flags = ((native.SB_PLACE_FROM_REFERENCE if from_reference else 0) | (native.SB_PLACE_KEEP_PINNED if keep_pinned else 0)
+               | (native.SB_PLACE_SET_VELOCITY if (lin is not None or ang is not None) else 0))
+    p.m[:] = np.asarray(np.eye(3) if m is None else m, np.float32).reshape(9).tolist()
+    p.frm[:] = np.asarray(frm, np.float32).reshape(3).tolist()
+    p.to[:] = np.asarray(to, np.float32).reshape(3).tolist()
+    p.lin[:] = np.asarray((0, 0, 0) if lin is None else lin, np.float32).reshape(3).tolist()
+    p.ang[:] = np.asarray((0, 0, 0) if ang is None else ang, np.float32).reshape(3).tolist()
+    return p
+
+
 def _uv_args(uv):
     """-> (uv (count,2) float32 or None, count) as sb_set_render_uvs takes them"""
     if uv is None:
@@ -532,6 +556,14 @@ class SoftbodyGroup:
     def apply_impulses(self, items):
         """Softbody.apply_impulses in the whole mesh's numbering; SURFACE items against the group's triangles / embedding."""
         _apply_impulses(native.lib().sb_group_apply_impulses, self._g, items)
+
+    def place(self, m=None, frm=(0, 0, 0), to=(0, 0, 0), lin=None, ang=None, from_reference=False, keep_pinned=False):
+        """Move, rotate or respawn the whole body between two ticks, on the devices (sb_group_place, SPEC.md 2d): x' = m (src - frm) + to with
+        src the positions, or the reference pose under from_reference (a respawn: undeformed). Velocities turn with m, or -- lin / ang given, and
+        always under from_reference -- become lin + ang x (x' - to). Pinned particles move along unless keep_pinned. m: (3, 3), any finite
+        matrix (placement_from_rotation builds one from a quaternion); None = identity. A prepared native.SbPlacement may be given as m."""
+        p = m if isinstance(m, native.SbPlacement) else make_placement(m, frm, to, lin, ang, from_reference, keep_pinned)
+        check(native.lib().sb_group_place(self._g, C.byref(p)))
 
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
