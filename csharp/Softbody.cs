@@ -39,6 +39,15 @@ namespace SoftbodyMI355X
         [SerializeField] bool groundPlane = false;
         [SerializeField] Vector3 groundNormal = new Vector3(0f, 1f, 0f);
         [SerializeField] float groundOffset = 0f;
+        [Header("Air (SPEC.md 2e: on the render triangles, before every tick; all zero = off)")]
+        [Tooltip("Air velocity in world space. Felt through airDragNormal / airDragTangential.")]
+        public Vector3 wind = Vector3.zero;
+        [Tooltip("Drag along a triangle's normal, per unit area (>= 0). Larger than airDragTangential makes a sail. Explicit: keep inverse mass * fixedDeltaTime * drag * (a particle's incident area / 3) below 1.")]
+        public float airDragNormal = 0f;
+        [Tooltip("Drag across a triangle's normal, per unit area (>= 0).")]
+        public float airDragTangential = 0f;
+        [Tooltip("Pressure along the winding's outward normal, per unit area: inflates a closed skin (negative deflates).")]
+        public float internalPressure = 0f;
         [Header("Device")]
         [SerializeField] bool useGpu = true;
         [Tooltip("First HIP device ordinal; with deviceCount > 1 the body is split spatially over devices device .. device + deviceCount - 1.")]
@@ -224,6 +233,7 @@ namespace SoftbodyMI355X
         void FixedUpdate()
         {
             SendImpulses();      // everything queued since the last tick, in one call, before the step
+            ApplySurfaceForces();      // wind, air drag, pressure: on the velocities the impulses left, before the step
             bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
             {
@@ -465,6 +475,20 @@ namespace SoftbodyMI355X
             bodyHas = 0;
             if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_impulses(handle, impulseQueue, count), "sb_group_apply_impulses");
             else if (cpu != null) cpu.ApplyImpulses(impulseQueue, count, renderTriangles);
+        }
+
+        /// <summary>Wind, air drag and pressure on the render triangles for one tick (SPEC.md 2e, sb_group_apply_surface_forces): nothing is sent
+        /// while all four inspector fields are zero, so a body without air keeps its fused ticks. One GPU, render triangles, no visualMesh (an
+        /// embedding and a partitioned body are unsupported by the plugin: the error is thrown, not worked around on the host). CPU branch:
+        /// the same section 2e in SoftbodyCpuSolver.</summary>
+        void ApplySurfaceForces()
+        {
+            if (wind == Vector3.zero && airDragNormal == 0f && airDragTangential == 0f && internalPressure == 0f) return;
+            Vector3 w = worldToSim.MultiplyVector(wind);
+            var f = new SbSurfaceForce { windX = w.x, windY = w.y, windZ = w.z, normal = airDragNormal, tangential = airDragTangential,
+                                         pressure = internalPressure, dt = Time.fixedDeltaTime };
+            if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_surface_forces(handle, ref f), "sb_group_apply_surface_forces");
+            else if (cpu != null) cpu.ApplySurfaceForces(f, renderTriangles);
         }
 
         /// <summary>transform.position / rotation = ... (Rigidbody.MovePosition + MoveRotation) for the soft body, between two ticks and on the GPUs

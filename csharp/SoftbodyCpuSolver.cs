@@ -145,6 +145,61 @@ namespace SoftbodyMI355X
             }
         }
 
+        // SPEC.md 2e: wind, air drag and pressure on the render triangles `tri` (particle indices) between two ticks, velocities only. Phase 1
+        // computes every triangle's J from the state as it is before the call, phase 2 adds them per particle in ascending triangle order,
+        // once per corner slot. The validation is the plugin's (softbody_group.h), here as exceptions before anything is applied.
+        public void ApplySurfaceForces(SbSurfaceForce f, int[] tri)
+        {
+            Vector3[] x = sb.positions; Vector3[] v = sb.velocities; float[] w = sb.inverseMass;
+            int n = x.Length, m = tri != null ? tri.Length / 3 : 0;
+            if (f.flags != 0 || f.reserved0 != 0 || f.reserved1 != 0 || f.reserved2 != 0) throw new ArgumentException("surface force: flags and reserved must be 0");
+            if (!Finite(f.windX) || !Finite(f.windY) || !Finite(f.windZ) || !Finite(f.normal) || !Finite(f.tangential) || !Finite(f.pressure) || !Finite(f.dt))
+                throw new ArgumentException("surface force: NaN or infinite value");
+            if (f.normal < 0f || f.tangential < 0f || !(f.dt > 0f)) throw new ArgumentException("surface force: normal and tangential must not be negative, dt must be positive");
+            if (m == 0) throw new InvalidOperationException("surface force: no render triangles are set");
+            float hn = (float)((float)(f.dt * f.normal) / 6.0f), ht = (float)((float)(f.dt * f.tangential) / 6.0f), hp = (float)((float)(f.dt * f.pressure) / 6.0f);
+            var J = new Vector3[m];
+            var skipped = new bool[m];
+            for (int t = 0; t < m; ++t)
+            {
+                int a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
+                float e1x = (float)(x[b].x - x[a].x), e1y = (float)(x[b].y - x[a].y), e1z = (float)(x[b].z - x[a].z);
+                float e2x = (float)(x[c].x - x[a].x), e2y = (float)(x[c].y - x[a].y), e2z = (float)(x[c].z - x[a].z);
+                float fx = (float)((float)(e1y * e2z) - (float)(e1z * e2y)), fy = (float)((float)(e1z * e2x) - (float)(e1x * e2z)), fz = (float)((float)(e1x * e2y) - (float)(e1y * e2x));
+                float L2 = (float)((float)((float)(fx * fx) + (float)(fy * fy)) + (float)(fz * fz));
+                if (!(L2 >= 1.262177448e-29f) || !(L2 < float.PositiveInfinity)) { skipped[t] = true; continue; }      // 0x1p-96f
+                float L = (float)Math.Sqrt(L2);      // (the double root of a float, rounded once more, is the correctly rounded float root)
+                float ux = (float)(f.windX - (float)((float)((float)(v[a].x + v[b].x) + v[c].x) / 3.0f));
+                float uy = (float)(f.windY - (float)((float)((float)(v[a].y + v[b].y) + v[c].y) / 3.0f));
+                float uz = (float)(f.windZ - (float)((float)((float)(v[a].z + v[b].z) + v[c].z) / 3.0f));
+                float uf = (float)((float)((float)(ux * fx) + (float)(uy * fy)) + (float)(uz * fz));
+                float q = (float)(uf / L2);
+                float unx = (float)(q * fx), uny = (float)(q * fy), unz = (float)(q * fz);
+                float utx = (float)(ux - unx), uty = (float)(uy - uny), utz = (float)(uz - unz);
+                J[t] = new Vector3((float)((float)(L * (float)((float)(hn * unx) + (float)(ht * utx))) + (float)(hp * fx)),
+                                   (float)((float)(L * (float)((float)(hn * uny) + (float)(ht * uty))) + (float)(hp * fy)),
+                                   (float)((float)(L * (float)((float)(hn * unz) + (float)(ht * utz))) + (float)(hp * fz)));
+            }
+            var G = new Vector3[n];
+            var met = new bool[n];
+            for (int t = 0; t < m; ++t)
+            {
+                if (skipped[t]) continue;
+                for (int k = 0; k < 3; ++k)
+                {
+                    int p = tri[3 * t + k];
+                    G[p] = new Vector3((float)(G[p].x + J[t].x), (float)(G[p].y + J[t].y), (float)(G[p].z + J[t].z));
+                    met[p] = true;
+                }
+            }
+            for (int p = 0; p < n; ++p)
+            {
+                if (!met[p] || !(w[p] > 0f)) continue;
+                float ax = (float)(w[p] * G[p].x), ay = (float)(w[p] * G[p].y), az = (float)(w[p] * G[p].z);
+                v[p] = new Vector3(Canonical((float)(v[p].x + ax)), Canonical((float)(v[p].y + ay)), Canonical((float)(v[p].z + az)));
+            }
+        }
+
         static bool Finite(float f) { return !(float.IsNaN(f) || float.IsInfinity(f)); }
 
         // v_p.c = v_p.c + (we_p * G.c); a pinned particle is skipped

@@ -137,6 +137,18 @@ namespace SoftbodyMI355X
         public int reserved0, reserved1;
     }
 
+    /// <summary>sb_surface_force (44 bytes): the record of sb_group_apply_surface_forces (SPEC.md 2e). wind: air velocity in
+    /// simulation space; normal, tangential: drag coefficients along and across a triangle's normal (>= 0); pressure: along the winding's right-hand
+    /// normal; dt: the time the force acts for (> 0). flags and reserved stay 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbSurfaceForce
+    {
+        public float windX, windY, windZ;
+        public float normal, tangential, pressure, dt;
+        public uint flags;
+        public int reserved0, reserved1, reserved2;
+    }
+
     /// <summary>sb_body_state (592 bytes): what sb_group_get_body_state / sb_group_body_state_from_sums fill (SPEC.md 6f). what = SoftbodyNative.BodyPose |
     /// BodyMotion as asked, flags = BodyNoMass | BodyDegeneratePose | BodyDegenerateInertia. sums: the 32 mass-weighted sums in binary64 (the header lists the slots);
     /// secondMoment about com (xx, yy, zz, xy, xz, yz); apq row-major; rotation: unit quaternion (x, y, z, w), w >= 0, reference pose -> simulation space;
@@ -294,6 +306,7 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_state(IntPtr g, IntPtr posXyz, IntPtr velXyz, int n);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_kinematic_positions(IntPtr g, IntPtr ids, IntPtr posXyz, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_apply_impulses(IntPtr g, SbImpulse[] items, int count);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_apply_surface_forces(IntPtr g, ref SbSurfaceForce force);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_triangles(IntPtr g, int[] triAbc, int m);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_embedding(IntPtr g, int[] cageIjkl, float[] weights4, int mVertices, int[] triAbc, int mTri);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_render_uvs(IntPtr g, IntPtr uv, int count);

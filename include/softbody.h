@@ -230,6 +230,11 @@ typedef struct {                 /* 48 bytes */
     int32_t  reserved[2];        /* must be 0 */
 } sb_impulse;
 int sb_apply_impulses(sb_solver *s, const sb_impulse *items, int32_t count);
+/* Surface forces between two ticks (wind, air drag, pressure on the render triangles; SPEC.md 2e) have no entry point on a solver handle,
+ * as placement and body state have none: sb_group_apply_surface_forces of softbody_group.h, on a group of one rank. They are unsupported
+ * while a render embedding is in force (its triangles index skinned vertices, which have no velocities of their own) and on a partitioned
+ * body (a triangle needs positions and velocities of corners that another rank owns, and no rank holds those at a tick's end --
+ * sb_readback_get_normals is unsupported on a rank for the same reason). */
 /* Asynchronous render readback: sb_readback_begin snapshots the positions as of every sb_step issued so far
  * (a small kernel on the compute stream) and starts a D2H copy into plugin-owned pinned memory on a second
  * stream; the next sb_step overlaps with that copy. sb_readback_end waits for the OLDEST pending snapshot and

@@ -92,6 +92,40 @@ int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const floa
  * every rank is handed its entries in order and in its numbering, RADIAL items go to every rank unchanged. Every rank completes its
  * tick's held-back last kernel, so the ranks stay in the same tick state. Both host models. */
 int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count);
+/* Surface forces between two ticks (SPEC.md 2e): wind, air drag and internal pressure on the render triangles of
+ * sb_group_set_render_triangles -- a cloth that flutters, a shell the air slows down, a closed skin that is inflated. One call applies one
+ * record to every triangle, from the tick-end positions and velocities, in binary32 without FMA. Per triangle with unit normal n (right-hand
+ * rule of its winding), area A, velocity vt = the mean of its corners' and u = wind - vt:
+ *     F = A * (normal * (u.n) n + tangential * (u - (u.n) n)) + pressure * A * n
+ * and every corner takes a third of the impulse dt * F, times its inverse mass. The force is linear in u (plain drag): normal > tangential
+ * makes a sail, wind = 0 is still-air drag, pressure pushes along n. Every triangle is evaluated on the state as it was before the call;
+ * a particle then adds its incident triangles' shares in ascending triangle order, once per corner slot that names it. A triangle whose
+ * doubled area squared is below 2^-96, infinite or NaN is skipped. A pinned particle (inverse mass 0), a particle in no triangle and a
+ * particle in skipped triangles only keep their velocity's bits; positions never change. A velocity component that comes out NaN is stored
+ * as the quiet NaN 0x7fc00000 (SPEC.md 2c).
+ * The scheme is explicit: a particle overshoots once inverse mass * dt * max(normal, tangential) * (incident area / 3) exceeds 1 -- the
+ * caller's choice of coefficients.
+ * Errors, all before anything changes (the record is checked before the group is touched): SB_ERR_INVALID_ARG for a null argument, a
+ * non-zero flag or reserved field, a NaN or infinite wind, normal, tangential, pressure or dt, normal < 0, tangential < 0, dt <= 0;
+ * SB_ERR_STATE before sb_group_finalize and while no render triangles are set; SB_ERR_UNSUPPORTED while a render embedding is in force (its
+ * triangles index skinned vertices, which have no velocities of their own) and on a group of more than one rank (a partitioned body's
+ * triangle needs positions and velocities of corners that another rank owns, and no rank holds those at a tick's end --
+ * sb_readback_get_normals is unsupported on a rank for the same reason). Neither limit has a host fallback. A refused call leaves every bit
+ * of the state as it was, and the tick's last kernel held back.
+ * Asynchronous like sb_group_step (two kernels on the rank's stream). Velocities exist only once a tick is complete, so the call completes
+ * the tick's held-back last kernel (and lands pending kinematic targets) first: THE NEXT sb_group_step STARTS UNFUSED, as after
+ * sb_group_apply_impulses. The tables (triangles in device numbering, incident lists, 16 bytes of scratch per triangle) are built at the
+ * first call after sb_group_set_render_triangles and released by the next sb_group_set_render_triangles; they count in the rank's
+ * sb_stats.device_bytes. Nothing is allocated before the first call. */
+typedef struct {                 /* 44 bytes */
+    float    wind[3];            /* air velocity, world space */
+    float    normal, tangential; /* drag coefficients along and across the triangle's normal, >= 0 */
+    float    pressure;           /* along the winding's right-hand normal; negative deflates */
+    float    dt;                 /* > 0: the time the force acts for (the tick's dt) */
+    uint32_t flags;              /* none defined: must be 0 */
+    int32_t  reserved[3];        /* must be 0 */
+} sb_surface_force;
+int sb_group_apply_surface_forces(sb_group *g, const sb_surface_force *force);
 
 /* ---- render readback (same contract as sb_readback_* / sb_set_render_triangles of softbody.h) -------------------------------------------- */
 /* Every rank snapshots the particles it owns (peeking while its tick's last kernel is held back) straight into ONE buffer on the render device

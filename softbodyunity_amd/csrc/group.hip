@@ -555,6 +555,29 @@ int sb_group_apply_impulses(sb_group *g, const sb_impulse *items, int32_t count)
     });
 }
 
+int sb_group_apply_surface_forces(sb_group *g, const sb_surface_force *f) {
+    // null and record checks before the group is touched: refused the same way on a machine without a device
+    if (!g || !f) return fail(SB_ERR_INVALID_ARG, "sb_group_apply_surface_forces: null argument");
+    if (int rc = validate_surface_force("sb_group_apply_surface_forces", f)) return rc;
+    if (int rc = check_group(g, true, "sb_group_apply_surface_forces")) return rc;
+    if (g->W > 1)
+        return fail(SB_ERR_UNSUPPORTED, "sb_group_apply_surface_forces: a group of more than one rank (a triangle needs positions and velocities of corners that "
+                    "another rank owns, and no rank holds those at a tick's end)");
+    if (g->render.emb.m > 0)
+        return fail(SB_ERR_UNSUPPORTED, "sb_group_apply_surface_forces: a render embedding is in force (its triangles index skinned vertices, which have no velocities of their own)");
+    if (g->render.tri.empty()) return fail(SB_ERR_STATE, "sb_group_apply_surface_forces: no render triangles are set (sb_group_set_render_triangles comes first)");
+    return guarded([&]() -> int {
+        // the one rank holds the whole body; the triangles are the group's, handed over in the rank's numbering while its tables are not built
+        sb_solver *s = g->ranks[0];
+        std::vector<int32_t> tri;
+        if (!surface_tables_built(s)) {
+            tri.resize(g->render.tri.size());
+            for (size_t c = 0; c < tri.size(); ++c) tri[c] = g->index_in_rank[(size_t)g->render.tri[c]];
+        }
+        return apply_surface_forces_validated(s, *f, tri.data(), (int64_t)(g->render.tri.size() / 3));
+    });
+}
+
 int sb_group_place(sb_group *g, const sb_placement *p) {
     // null and struct checks before the group is touched: refused the same way on a machine without a device
     if (!g || !p) return fail(SB_ERR_INVALID_ARG, "sb_group_place: null argument");
@@ -576,7 +599,9 @@ int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {
         return fail(SB_ERR_STATE, "sb_group_set_render_triangles: a render embedding is set (switch it off first: sb_group_set_render_embedding with m_vertices = 0)");
     return guarded([&]() -> int {
         if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));
-        return set_render_triangles("sb_group_set_render_triangles", g->render, g->mesh->n, tri, m);
+        const int rc = set_render_triangles("sb_group_set_render_triangles", g->render, g->mesh->n, tri, m);
+        if (rc == SB_OK) for (sb_solver *s : g->ranks) if (s) release_surface_tables(s);       // (the surface forces' tables of the old list; only a single rank has any)
+        return rc;
     });
 }
 

@@ -3,7 +3,7 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), stream_codec.hpp (the bit layout of the tile constraint stream: the builder's encoders, the kernels' and the validator's decoders), tables.hip (their upload), launch_shape.hpp (which tile_kernel
-// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), placement.hip (placement between two ticks: one affine map over the whole body), render.hip (render readback: the stage and the entry-point bodies a solver
+// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), surface_force.hip (wind, air drag and pressure on the render triangles between two ticks), placement.hip (placement between two ticks: one affine map over the whole body), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
 // window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
@@ -108,6 +108,15 @@ struct DevTiling : sbt::TilingScalars {
     DevBuf<int2> runs_overflow;
     DevBuf<uint32_t> stream;     // per tile: [round words][rest-length dictionary][round data], see stream_codec.hpp
     DevBuf<int32_t> gather;      // T2: particle lists of the tiles (local numbering)
+};
+
+// Surface forces (sb_group_apply_surface_forces, surface_force.hip; SPEC.md 2e): the render triangles in device numbering, the render particles
+// with their incident-triangle lists (ascending t, one entry per corner slot) and one float4 of scratch per triangle. Built at the first
+// call after the triangles changed, released when they change; `bytes` is their share of sb_stats.device_bytes (0 = not built).
+struct SurfaceForceTables {
+    DevBuf<int32_t> d_tri, d_part, d_off, d_adj;
+    DevBuf<float4> d_J;
+    int64_t m = 0, n_part = 0, bytes = 0;
 };
 
 struct DevGColour {
@@ -277,6 +286,8 @@ struct sb_solver {
     bool kin_fuse = true;                  // !SB_TUNE_NO_KIN_FUSE (A/B: pending targets always complete the previous tick first)
     // impulses (sb_apply_impulses, impulse.hip): the sparse kernels' tables travel like the kinematic targets, one table per call
     sbi::TableRing<4> imp_ring;
+    // surface forces (sb_group_apply_surface_forces, surface_force.hip): nothing before the first call
+    sbi::SurfaceForceTables surf;
     // Peek (world == 1): a position read while the tick's last kernel is deferred runs tile_kernel<kKindPeek> -- the same rounds + collide on
     // the same inputs, written to d_peek instead of the state -- so the deferred kernel can still be fused with the next tick's first
     // one. A render-set-only readback peeks only at the T0 tiles that hold a render particle (peek_tiles: copies of their descriptors).
@@ -374,6 +385,13 @@ int64_t impulse_triangles_in_force(const RenderState &R);       // triangles of 
 int validate_impulses(const char *who, const sb_impulse *items, int32_t count, int32_t n, int64_t m_tri, bool rank);
 void expand_impulses(const RenderState &R, const sb_impulse *items, int32_t count, std::vector<sb_impulse> &out);      // SURFACE -> PARTICLE-like entries
 int apply_impulses_validated(sb_solver *s, const sb_impulse *items, int32_t count);      // PARTICLE / RADIAL, the rank's numbering, owned particles
+
+// ---- surface_force.hip: wind, air drag and pressure on the render triangles between two ticks (SPEC.md 2e) ----------------------------------
+int validate_surface_force(const char *who, const sb_surface_force *f);      // the record alone: needs neither a solver nor a device
+bool surface_tables_built(const sb_solver *s);                               // false: the next call reads its triangle list
+// world == 1; tri: m render triangles in the rank's numbering (read only while the tables are not built); asynchronous on s->stream
+int apply_surface_forces_validated(sb_solver *s, const sb_surface_force &f, const int32_t *tri, int64_t m);
+void release_surface_tables(sb_solver *s);                                   // the render triangles changed
 
 // ---- placement.hip: placement between two ticks (SPEC.md 2d) -------------------------------------------------------------------------------
 int validate_placement(const char *who, const sb_placement *p);      // the struct alone: needs neither a group nor a device

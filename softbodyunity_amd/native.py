@@ -115,6 +115,12 @@ class SbImpulse(C.Structure):
                 ("vec", C.c_float * 3), ("radius", C.c_float), ("strength", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class SbSurfaceForce(C.Structure):
+    """sb_surface_force (44 bytes): the record of sb_group_apply_surface_forces (SPEC.md 2e); flags and reserved must be 0"""
+    _fields_ = [("wind", C.c_float * 3), ("normal", C.c_float), ("tangential", C.c_float), ("pressure", C.c_float), ("dt", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
 class SbBodyState(C.Structure):
     """sb_body_state (592 bytes): what sb_group_get_body_state / sb_group_body_state_from_sums fill (SPEC.md 6f)"""
     _fields_ = [("n_dynamic", C.c_int64), ("n_pinned", C.c_int64), ("what", C.c_uint32), ("flags", C.c_uint32), ("sums", C.c_double * 32),
@@ -242,6 +248,7 @@ SIGNATURES = {
     "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
+    "sb_group_apply_surface_forces": (C.c_int, [_P, C.POINTER(SbSurfaceForce)]),
     "sb_group_place": (C.c_int, [_P, C.POINTER(SbPlacement)]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),

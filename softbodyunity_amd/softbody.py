@@ -396,6 +396,14 @@ def _apply_impulses(fn, handle, items):
     check(fn(handle, items.ctypes.data_as(C.POINTER(native.SbImpulse)), int(items.shape[0])))
 
 
+def make_surface_force(wind=(0, 0, 0), normal=0.0, tangential=0.0, pressure=0.0, dt=0.02):
+    """-> native.SbSurfaceForce (SPEC.md 2e): the record of one apply_surface_forces call, every value rounded to binary32 once"""
+    f = native.SbSurfaceForce()
+    f.wind[:] = np.asarray(wind, np.float32).reshape(3).tolist()
+    f.normal, f.tangential, f.pressure, f.dt = normal, tangential, pressure, dt
+    return f
+
+
 def placement_from_rotation(quat_xyzw, scale=1.0):
     """-> the (3, 3) float32 matrix SoftbodyGroup.place takes as m: the rotation of a quaternion (x, y, z, w) -- normalised here, computed in
     binary64 and rounded once -- times a uniform scale (rest lengths do not scale: a scaled body is squashed and recovers)."""
@@ -556,6 +564,15 @@ class SoftbodyGroup:
     def apply_impulses(self, items):
         """Softbody.apply_impulses in the whole mesh's numbering; SURFACE items against the group's triangles / embedding."""
         _apply_impulses(native.lib().sb_group_apply_impulses, self._g, items)
+
+    def apply_surface_forces(self, wind=(0, 0, 0), normal=0.0, tangential=0.0, pressure=0.0, dt=None):
+        """Wind, air drag and pressure on the render triangles between two ticks (sb_group_apply_surface_forces, SPEC.md 2e): per triangle of
+        area A and unit normal n the force A (normal (u.n) n + tangential (u - (u.n) n)) + pressure A n, u = wind - the triangle's velocity,
+        acts for dt (None = the fixed delta time) and is shared in thirds by the corners. Velocities change, positions do not; the next step
+        starts unfused. A group of one rank; more ranks and a render embedding are unsupported. A prepared native.SbSurfaceForce may be
+        given as wind."""
+        f = wind if isinstance(wind, native.SbSurfaceForce) else make_surface_force(wind, normal, tangential, pressure, self.fixed_delta_time if dt is None else dt)
+        check(native.lib().sb_group_apply_surface_forces(self._g, C.byref(f)))
 
     def place(self, m=None, frm=(0, 0, 0), to=(0, 0, 0), lin=None, ang=None, from_reference=False, keep_pinned=False):
         """Move, rotate or respawn the whole body between two ticks, on the devices (sb_group_place, SPEC.md 2d): x' = m (src - frm) + to with
