@@ -95,6 +95,8 @@ namespace SoftbodyMI355X
         int[] hitTriangles;                    // the triangles the plugin casts rays against, in the numbering of positions / normals
         readonly float[] rayBuffer = new float[8];
         readonly SbRayHit[] hitBuffer = new SbRayHit[1];
+        readonly float[] queryBuffer = new float[4];
+        readonly SbClosestHit[] closestBuffer = new SbClosestHit[1];
         SbImpulse[] impulseQueue = new SbImpulse[16];      // AddImpulse / AddImpulseAtHit / AddExplosionImpulse since the last FixedUpdate, in call order
         int impulseCount;
         // body state (SPEC.md 6f): what has been asked of the state the last tick left (bodyHas: BodyPose / BodyMotion bits), cached until the next tick or impulse
@@ -429,6 +431,47 @@ namespace SoftbodyMI355X
                                           : Vector3.Cross(positions[b] - positions[a], positions[c] - positions[a]);
             hit.normal = SimToWorldDirection(nrm).normalized;
             return true;
+        }
+
+        /// <summary>Collider.ClosestPoint for the deforming body: the point of the render mesh nearest to worldPoint, on the GPU against the
+        /// triangles of the snapshot on screen (SPEC.md 6g, sb_group_readback_closest_points: synchronous, brute force over every triangle) -- on
+        /// the CPU path the same chain over the arrays the component holds. Same preconditions as Raycast; false where nothing lies within
+        /// maxDistance (float.PositiveInfinity: no limit). hit.distance is the distance to the surface -- for a sphere of radius r around
+        /// worldPoint the penetration is r - hit.distance --, point and interpolated normal as Raycast gives them, and AddImpulseAtHit takes
+        /// the hit as it is. Distances are those of the component's local space.</summary>
+        public bool ClosestPoint(Vector3 worldPoint, float maxDistance, out SoftbodyHit hit)
+        {
+            hit = default(SoftbodyHit);
+            int[] tris = handle != IntPtr.Zero ? hitTriangles : renderTriangles;      // (the CPU path keeps the particles' own numbering)
+            if (tris == null || tris.Length < 3) return false;
+            Vector3 q = WorldToSimPoint(worldPoint);
+            SbClosestHit h;
+            if (handle != IntPtr.Zero)
+            {
+                if (!haveBounds) return false;      // (haveBounds: a snapshot has ended)
+                queryBuffer[0] = q.x; queryBuffer[1] = q.y; queryBuffer[2] = q.z; queryBuffer[3] = maxDistance;
+                SoftbodyNative.Check(SoftbodyNative.sb_group_readback_closest_points(handle, queryBuffer, 1, closestBuffer), "sb_group_readback_closest_points");
+                h = closestBuffer[0];
+            }
+            else if (cpu != null) h = SoftbodyCpuSolver.ClosestPoint(positions, tris, q, maxDistance);
+            else return false;
+            if (h.triangle < 0) return false;
+            int a = tris[3 * h.triangle], b = tris[3 * h.triangle + 1], c = tris[3 * h.triangle + 2];
+            float wa = 1f - h.u - h.v;
+            hit.triangle = h.triangle; hit.distance = h.distance; hit.barycentric = new Vector3(wa, h.u, h.v);
+            hit.point = SimToWorldPoint(wa * positions[a] + h.u * positions[b] + h.v * positions[c]);
+            Vector3 nrm = normals != null ? wa * normals[a] + h.u * normals[b] + h.v * normals[c]
+                                          : Vector3.Cross(positions[b] - positions[a], positions[c] - positions[a]);
+            hit.normal = SimToWorldDirection(nrm).normalized;
+            return true;
+        }
+
+        /// <summary>Physics.CheckSphere for the deforming body: does the sphere touch the render mesh of the snapshot on screen? One
+        /// ClosestPoint query limited to the radius.</summary>
+        public bool CheckSphere(Vector3 centre, float radius)
+        {
+            SoftbodyHit hit;
+            return ClosestPoint(centre, radius, out hit);
         }
 
         /// <summary>Rigidbody.AddForce(impulse, ForceMode.Impulse) for one particle (velocityChange: ForceMode.VelocityChange -- the mass is

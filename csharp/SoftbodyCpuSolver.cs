@@ -200,6 +200,44 @@ namespace SoftbodyMI355X
             }
         }
 
+        // SPEC.md 6g: the nearest point of the triangles `tri` (indices into `p`) to q, the sequential loop -- per triangle the Voronoi-region
+        // chain, the first test that holds deciding (u, v); a candidate iff dd <= maxDistance^2 and dd is finite; the smallest dd wins, among
+        // equal ones the first triangle. A miss: triangle = -1, distance = u = v = 0. The validation is the plugin's (softbody_group.h).
+        public static SbClosestHit ClosestPoint(Vector3[] p, int[] tri, Vector3 q, float maxDistance)
+        {
+            if (!Finite(q.x) || !Finite(q.y) || !Finite(q.z)) throw new ArgumentException("closest point: NaN or infinite coordinate");
+            if (!(maxDistance >= 0f)) throw new ArgumentException("closest point: max_distance is NaN or negative");
+            int m = tri != null ? tri.Length / 3 : 0;
+            float R2 = (float)(maxDistance * maxDistance);
+            var best = new SbClosestHit { triangle = -1 };
+            float bestDd = 0f;
+            for (int t = 0; t < m; ++t)
+            {
+                Vector3 pa = p[tri[3 * t]], pb = p[tri[3 * t + 1]], pc = p[tri[3 * t + 2]];
+                F3 ab = Sub(pb, pa), ac = Sub(pc, pa), ap = Sub(q, pa), bp = Sub(q, pb), cp = Sub(q, pc);
+                float d1 = Dot(ab, ap), d2 = Dot(ac, ap), d3 = Dot(ab, bp), d4 = Dot(ac, bp), d5 = Dot(ab, cp), d6 = Dot(ac, cp);
+                float vc = (float)((float)(d1 * d4) - (float)(d3 * d2)), vb = (float)((float)(d5 * d2) - (float)(d1 * d6)), va = (float)((float)(d3 * d6) - (float)(d5 * d4));
+                float e = (float)(d4 - d3), f = (float)(d5 - d6);
+                float u, v;
+                if (d1 <= 0f && d2 <= 0f) { u = 0f; v = 0f; }
+                else if (d3 >= 0f && d4 <= d3) { u = 1f; v = 0f; }
+                else if (vc <= 0f && d1 >= 0f && d3 <= 0f) { u = (float)(d1 / (float)(d1 - d3)); v = 0f; }
+                else if (d6 >= 0f && d5 <= d6) { u = 0f; v = 1f; }
+                else if (vb <= 0f && d2 >= 0f && d6 <= 0f) { u = 0f; v = (float)(d2 / (float)(d2 - d6)); }
+                else if (va <= 0f && e >= 0f && f >= 0f) { float w = (float)(e / (float)(e + f)); u = (float)(1.0f - w); v = w; }
+                else { float den = (float)(1.0f / (float)((float)(va + vb) + vc)); u = (float)(vb * den); v = (float)(vc * den); }
+                float cx = (float)(pa.x + (float)((float)(u * ab.x) + (float)(v * ac.x)));
+                float cy = (float)(pa.y + (float)((float)(u * ab.y) + (float)(v * ac.y)));
+                float cz = (float)(pa.z + (float)((float)(u * ab.z) + (float)(v * ac.z)));
+                F3 r = new F3((float)(q.x - cx), (float)(q.y - cy), (float)(q.z - cz));
+                float dd = Dot(r, r);
+                if (!(dd <= R2 && dd < float.PositiveInfinity)) continue;
+                if (best.triangle < 0 || dd < bestDd) { best.triangle = t; best.u = u; best.v = v; bestDd = dd; }
+            }
+            if (best.triangle >= 0) best.distance = (float)Math.Sqrt(bestDd);      // (the double root of a float, rounded once more, is the correctly rounded float root)
+            return best;
+        }
+
         static bool Finite(float f) { return !(float.IsNaN(f) || float.IsInfinity(f)); }
 
         // v_p.c = v_p.c + (we_p * G.c); a pinned particle is skipped

@@ -122,6 +122,15 @@ namespace SoftbodyMI355X
         public float t, u, v;
     }
 
+    /// <summary>sb_closest_hit (16 bytes, the layout of SbRayHit): the nearest point of the render mesh to one query (SPEC.md 6g); triangle = -1
+    /// where nothing lies within max_distance. (u, v) barycentric as in SbRayHit: point = (1 - u - v) p[a] + u p[b] + v p[c].</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbClosestHit
+    {
+        public int triangle;
+        public float distance, u, v;
+    }
+
     /// <summary>sb_impulse (48 bytes): one item of sb_apply_impulses / sb_group_apply_impulses (SPEC.md 2c). kind = SoftbodyNative.SB_IMPULSE_PARTICLE / _SURFACE / _RADIAL, flags = SB_IMPULSE_VELOCITY_CHANGE | SB_IMPULSE_LINEAR_FALLOFF;
     /// PARTICLE: index = particle, vec = J; SURFACE: index = triangle (-1 skips the item), (u, v) as SbRayHit gives them, vec = J;
     /// RADIAL: vec = centre, radius, strength. reserved stays 0.</summary>
@@ -320,6 +329,8 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_bounds(IntPtr g, [Out] float[] loXyz, [Out] float[] hiXyz);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_raycast(IntPtr g, float[] rays, int count, [Out] SbRayHit[] hits);
+        // queries: 4 floats each = x, y, z, max_distance (SPEC.md 6g)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_closest_points(IntPtr g, float[] queries, int count, [Out] SbClosestHit[] hits);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_place(IntPtr g, ref SbPlacement placement);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);

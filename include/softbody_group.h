@@ -158,6 +158,28 @@ int sb_group_get_bounds(sb_group *g, float lo_xyz[3], float hi_xyz[3]);
 /* Ray casts (sb_readback_raycast, SPEC.md 6e), same contract, against the snapshot the last sb_group_readback_end returned: on the render
  * device, on the gathered snapshot (whole array or render set) or the skinned vertices, in both host models -- the ranks take no part. */
 int sb_group_readback_raycast(sb_group *g, const float *rays /* 8 floats per ray */, int32_t count, sb_ray_hit *hits_out);
+/* Closest points (SPEC.md 6g): what Collider.ClosestPoint, Physics.CheckSphere and Physics.OverlapSphere are to a rigid body, for the deformed
+ * render mesh -- the ray cast's twin. For each query (x, y, z, max_distance), world space, the nearest point on the triangles of the snapshot
+ * the last sb_group_readback_end returned: the render triangles over the gathered snapshot (whole array or render set), or the embedding's
+ * triangles over the skinned vertices. Brute force over every triangle on the render device, two launches per batch of 256 queries and no
+ * atomics; per triangle the closest point by its Voronoi regions (vertex, edge, face), in binary32 without FMA, bit for bit SPEC.md 6g.
+ *  - hits_out[r] = {triangle, distance, u, v}: point = (1 - u - v) p[a] + u p[b] + v p[c] with (a, b, c) the triangle's corners, exactly
+ *    what sb_ray_hit's (u, v) mean, so triangle, u, v go into an SB_IMPULSE_SURFACE item unchanged (penetration of a sphere of radius r:
+ *    r - distance; INTEGRATION.md has the loop). Among equally near triangles the lowest index. Nothing within max_distance: -1, 0, 0, 0.
+ *  - The limit is compared squared: a triangle is a candidate iff dd <= max_distance * max_distance (and dd is finite), dd the squared
+ *    distance in binary32; distance = sqrtf(dd) of the winner. max_distance = 0 finds only points on the surface (dd == 0); +inf is allowed.
+ *  - A triangle with a NaN or infinite corner is never returned and removes nothing else. Known limitation: a triangle whose deciding
+ *    region divides 0 by 0 -- a repeated corner, some collinear corners -- is no candidate either, although it has a nearest point.
+ *  - Synchronous, on the ray cast's stream and in its buffers (4 MB, allocated at the first cast or query and counted from then on; larger
+ *    counts walk in batches). It answers for the snapshot ended last whatever has been stepped or begun since, waits for no pending
+ *    snapshot, does not peek and leaves the tick's held-back last kernel alone: sb_stats.ticks_fused and readback_peeks do not change.
+ *  - SB_ERR_INVALID_ARG, nothing written to hits_out: a null group, count < 0, a null queries or hits_out with count > 0, a NaN or infinite
+ *    coordinate, a max_distance that is NaN or negative. SB_ERR_STATE exactly where sb_group_readback_raycast returns it: no readback has
+ *    ended, or the snapshot ended last has no triangles (taken without them, or the render mode was set again since). count = 0 returns
+ *    SB_OK once the state checks pass.
+ * The entry point is the group's only (a group of one rank is the plain solver, as for sb_group_place). Both host models; the ranks take no part. */
+typedef struct { int32_t triangle; float distance, u, v; } sb_closest_hit;      /* 16 bytes, the layout of sb_ray_hit; triangle = -1: nothing within max_distance */
+int sb_group_readback_closest_points(sb_group *g, const float *queries /* 4 floats per query: x, y, z, max_distance */, int32_t count, sb_closest_hit *hits_out);
 
 /* ---- body state: where the body is and how it moves (SPEC.md 6f) ------------------------------------------------------------------------- */
 /* What Rigidbody.worldCenterOfMass / .velocity / .angularVelocity and transform.position / rotation are to a rigid body, for a soft one:

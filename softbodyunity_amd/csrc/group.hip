@@ -848,6 +848,14 @@ int sb_group_readback_raycast(sb_group *g, const float *rays, int32_t count, sb_
     });
 }
 
+int sb_group_readback_closest_points(sb_group *g, const float *queries, int32_t count, sb_closest_hit *hits_out) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_closest_points: null group");
+    return guarded([&]() -> int {
+        if (g->render.copy_stream) HIP_CHECK(hipSetDevice(g->device_of(0)));       // the render device, in both host models: the ranks take no part
+        return readback_closest_points("sb_group_readback_closest_points", g->render, queries, count, hits_out, g->dev_bytes);
+    });
+}
+
 int sb_group_readback_get_render_set(sb_group *g, const int32_t **ids, int32_t *count) {
     if (!g || !ids || !count) return fail(SB_ERR_INVALID_ARG, "sb_group_readback_get_render_set: null argument");
     return readback_get_render_set("sb_group_readback_get_render_set", g->render, ids, count);

@@ -6,6 +6,7 @@
 // [BUILDER-DEFINED] boundary of SURVEY.md §8b (include/softbody*.h).
 #include "solver_internal.hpp"
 #include "readback_kernels.hip.hpp"
+#include "closest_kernels.hip.hpp"
 
 using namespace sbi;
 
@@ -63,6 +64,7 @@ void launch_bounds(hipStream_t st, ReadbackBounds &B, int slot, const float *xyz
 }
 
 static_assert(sizeof(sb_ray_hit) == sizeof(uint4), "raycast_final_kernel writes an sb_ray_hit as one 16-byte store");
+static_assert(sizeof(sb_closest_hit) == sizeof(uint4), "closest_final_kernel writes an sb_closest_hit as one 16-byte store");
 
 void ReadbackRaycast::prepare(int64_t &acct) {
     if (stream) return;
@@ -294,6 +296,44 @@ int readback_raycast(const char *who, RenderState &R, const float *rays, int32_t
         Q.hits.copy_out(Q.stream, (size_t)nb);
         HIP_CHECK(hipStreamSynchronize(Q.stream));
         std::memcpy(hits_out + done, Q.hits.h.p, (size_t)nb * sizeof(sb_ray_hit));
+    }
+    return SB_OK;
+}
+
+int readback_closest_points(const char *who, RenderState &R, const float *queries, int32_t count, sb_closest_hit *hits_out, int64_t &acct) {
+    const std::string me(who);
+    if (count < 0) return fail(SB_ERR_INVALID_ARG, me + ": negative count");
+    if (count > 0 && (!queries || !hits_out)) return fail(SB_ERR_INVALID_ARG, me + ": null pointer with a positive count");
+    for (int64_t r = 0; r < count; ++r) {       // every query before anything is written
+        const float *q = queries + 4 * r;
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(q[c])) return fail(SB_ERR_INVALID_ARG, me + ": a coordinate is NaN or infinite (query " + std::to_string(r) + ")");
+        if (!(q[3] >= 0.0f)) return fail(SB_ERR_INVALID_ARG, me + ": max_distance is NaN or negative (query " + std::to_string(r) + ")");
+    }
+    // the snapshot ended last, under the ray cast's condition (has_normals: taken with triangles in force, and they were not set again since)
+    const int k = R.last_ended;
+    if (k < 0) return fail(SB_ERR_STATE, me + ": no readback has ended");
+    if (!R.slot[k].has_normals)
+        return fail(SB_ERR_STATE, me + ": the snapshot ended last has no triangles to query (taken without render triangles, or the render mode was set again since)");
+    if (count == 0) return SB_OK;
+    const bool embedded = R.slot[k].embedded;
+    const float *xyz = embedded ? R.emb.pos[k].d.p : R.pos[k].d.p;
+    const RenderTopology &T = embedded ? R.emb.topo : R.topo;
+    const int m = (int)((embedded ? R.emb.tri.size() : R.tri.size()) / 3);
+    ReadbackRaycast &Q = R.ray;                 // the ray cast's stream and buffers: a batch of queries is half a batch of rays, the hits and partials are the same size
+    Q.prepare(acct);
+    const int groups = (int)std::min<int64_t>(((int64_t)m + sbk::kRayLanes - 1) / sbk::kRayLanes, sbk::kRayMaxGroups);
+    for (int64_t done = 0; done < count; done += sbk::kClosestBatch) {
+        const int nb = (int)std::min<int64_t>(count - done, sbk::kClosestBatch);
+        std::memcpy(Q.rays.h.p, queries + 4 * done, (size_t)nb * 4 * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(Q.rays.d.p, Q.rays.h.p, (size_t)nb * 4 * sizeof(float), hipMemcpyHostToDevice, Q.stream));
+        hipLaunchKernelGGL(sbk::closest_partial_kernel, dim3((unsigned)groups, (unsigned)((nb + sbk::kClosestTile - 1) / sbk::kClosestTile)), dim3(sbk::kRayLanes), 0, Q.stream, xyz,
+                           T.d_tri.p, m, Q.rays.d.p, nb, Q.d_partials.p);
+        hipLaunchKernelGGL(sbk::closest_final_kernel, dim3((unsigned)nb), dim3(sbk::kRayLanes), 0, Q.stream, Q.d_partials.p, groups, Q.hits.d.p);
+        HIP_CHECK(hipGetLastError());
+        Q.hits.copy_out(Q.stream, (size_t)nb);
+        HIP_CHECK(hipStreamSynchronize(Q.stream));
+        std::memcpy(hits_out + done, Q.hits.h.p, (size_t)nb * sizeof(sb_closest_hit));
     }
     return SB_OK;
 }

@@ -52,6 +52,7 @@ struct ReadbackBounds {
 
 // Ray casts (sb_readback_raycast, SPEC.md 6e): a stream of its own -- a cast waits for no pending snapshot's copy -- and, from the first cast
 // on, the buffers of one batch of rays: the rays and the hits with their pinned twins, the workgroups' partials. Larger counts walk in batches.
+// Closest-point queries (SPEC.md 6g) are synchronous on the same stream and stage their batches in the same buffers (first cast or query).
 struct ReadbackRaycast {
     Stream stream;
     Mirror<float> rays;                    // 8 floats per ray of a batch (the pinned side is the staging of the upload)
@@ -143,5 +144,7 @@ int readback_get_bounds(const char *who, const char *setter, RenderState &R, flo
 int readback_get_render_set(const char *who, RenderState &R, const int32_t **ids, int32_t *count);
 // SPEC.md 6e behind the owner's null-handle, world and device preconditions: `count` rays against the snapshot ended last, synchronous
 int readback_raycast(const char *who, RenderState &R, const float *rays, int32_t count, sb_ray_hit *hits_out, int64_t &acct);
+// SPEC.md 6g, the ray cast's twin on its stream and in its buffers: `count` queries (x, y, z, max_distance) against the snapshot ended last
+int readback_closest_points(const char *who, RenderState &R, const float *queries, int32_t count, sb_closest_hit *hits_out, int64_t &acct);
 
 }  // namespace sbi

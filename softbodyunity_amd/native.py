@@ -109,6 +109,11 @@ class SbRayHit(C.Structure):
     _fields_ = [("triangle", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
 
 
+class SbClosestHit(C.Structure):
+    """sb_closest_hit (16 bytes, the layout of sb_ray_hit): triangle = -1 where nothing lies within max_distance"""
+    _fields_ = [("triangle", C.c_int32), ("distance", C.c_float), ("u", C.c_float), ("v", C.c_float)]
+
+
 class SbImpulse(C.Structure):
     """sb_impulse (48 bytes): one item of sb_apply_impulses (SPEC.md 2c)"""
     _fields_ = [("kind", C.c_int32), ("flags", C.c_uint32), ("index", C.c_int32), ("u", C.c_float), ("v", C.c_float),
@@ -248,6 +253,7 @@ SIGNATURES = {
     "sb_group_readback_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_get_bounds": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sb_group_readback_raycast": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbRayHit)]),
+    "sb_group_readback_closest_points": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbClosestHit)]),
     "sb_group_apply_surface_forces": (C.c_int, [_P, C.POINTER(SbSurfaceForce)]),
     "sb_group_place": (C.c_int, [_P, C.POINTER(SbPlacement)]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),

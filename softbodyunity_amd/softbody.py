@@ -351,6 +351,19 @@ def _raycast(fn, handle, rays):
     return hits
 
 
+CLOSEST_HIT = np.dtype([("triangle", np.int32), ("distance", np.float32), ("u", np.float32), ("v", np.float32)])
+
+
+def make_closest_queries(points, max_distance=np.inf):
+    """-> (Q, 4) float32 = x, y, z, max_distance, as sb_group_readback_closest_points takes them (SPEC.md 6g): points (Q, 3) or (3,),
+    max_distance a scalar or one per point, rounded to binary32 once."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    q = np.zeros((points.shape[0], 4), np.float32)
+    q[:, 0:3] = points
+    q[:, 3] = np.asarray(max_distance, np.float32)
+    return q
+
+
 # sb_impulse as a numpy record (48 bytes, the layout of native.SbImpulse)
 IMPULSE = np.dtype([("kind", np.int32), ("flags", np.uint32), ("index", np.int32), ("u", np.float32), ("v", np.float32),
                     ("vec", np.float32, (3,)), ("radius", np.float32), ("strength", np.float32), ("reserved", np.int32, (2,))])
@@ -368,7 +381,8 @@ def impulse_particles(ids, vec, velocity_change=False):
 
 
 def impulse_hits(hits, vec, velocity_change=False):
-    """SURFACE items from the structured array raycast() returns, misses included (they are skipped): vec -- (3,) or (R, 3) -- at every hit."""
+    """SURFACE items from the structured array raycast() or closest_points() returns, misses included (they are skipped): vec -- (3,) or
+    (R, 3) -- at every hit."""
     hits = np.atleast_1d(hits)
     out = np.zeros(hits.shape[0], IMPULSE)
     out["kind"] = native.SB_IMPULSE_SURFACE
@@ -633,6 +647,18 @@ class SoftbodyGroup:
     def raycast(self, rays):
         """Softbody.raycast against the snapshot the group delivered last, on the render device."""
         return _raycast(native.lib().sb_group_readback_raycast, self._g, rays)
+
+    def closest_points(self, points, max_distance=np.inf):
+        """The nearest point of the deformed render mesh of the snapshot the group delivered last to each of points (SPEC.md 6g,
+        sb_group_readback_closest_points). points: (Q, 3) with max_distance a scalar or (Q,) -- or (Q, 4) rows x, y, z, max_distance as
+        make_closest_queries builds them. -> structured array (Q,) with fields triangle (int32, -1 = nothing within max_distance),
+        distance, u, v (float32): (u, v) barycentric in the triangle's corners b and c, as raycast() gives them, so impulse_hits takes
+        the array as it is."""
+        q = np.asarray(points, dtype=np.float32)
+        q = np.ascontiguousarray(q) if q.ndim == 2 and q.shape[1] == 4 else make_closest_queries(q, max_distance)
+        hits = np.zeros(q.shape[0], CLOSEST_HIT)
+        check(native.lib().sb_group_readback_closest_points(self._g, _fp(q), q.shape[0], hits.ctypes.data_as(C.POINTER(native.SbClosestHit))))
+        return hits
 
     def get_bounds(self):
         """-> (lo, hi): every rank's box of what it owns, combined on the host."""
