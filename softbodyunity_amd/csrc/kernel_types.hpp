@@ -75,6 +75,15 @@ constexpr bool kRegFullSlots = true;
 #endif
 constexpr bool kLanePackDecodable = kRegRoundsNarrow >= kLanePackRounds;       // else the host emits no lane-packed tile at all
 constexpr int kMaxRoundsLds = 128;   // round words cached in LDS; longer programs read them from memory
+// The lean coded kernels (tile_kernel's last template parameter; launch_shape.hpp use_lean_coded decides per solver): off, palette masses
+// (one index byte per particle), or one inverse mass for the whole launch.
+constexpr int kLeanOff = 0, kLeanPalette = 1, kLeanUniform = 2;
+// Build switch of A/B timing variants (make EXTRA=-D..., profiles/r16_lean_tuning_ab.txt):
+#ifdef SB_LEAN_NO_UNIFORM            // a uniform-mass launch runs the palette kernel
+constexpr bool kLeanUniformMass = false;
+#else
+constexpr bool kLeanUniformMass = true;
+#endif
 
 // Positions in HBM: packed xyz (12 B) + the static inverse mass in a side array (never rewritten).
 typedef float f32x3_t __attribute__((ext_vector_type(3)));

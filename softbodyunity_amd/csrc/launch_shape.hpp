@@ -67,4 +67,21 @@ inline bool use_prev_codes(const TilingScalars &T0, const TilingScalars &T1, con
     return tiling_always_narrow(T0, in.tile_lanes) && tiling_always_narrow(T1, in.tile_lanes);
 }
 
+// ---- the lean coded kernels (tile_kernel LEAN) --------------------------------------------------------------------------------------------
+// Decided with use_prev_codes, once per solver: every tile launch of the tick runs a lean kernel or none does. A lean kernel holds the
+// register-resident engine alone and reads a tile's slots only from the lane's own 16-byte word, so EVERY device tile of both tilings must
+// be lane-packed -- which, with palette masses, also makes it dictionary-coded (tables_host.cpp pack_form) -- and its program must fit the
+// registers of a 128-lane workgroup. A coded lattice with one rim pack that zips into more rounds keeps the general coded kernels.
+inline bool tiling_all_lane_packed(const TilingScalars &D) {
+    if (D.n_tiles == 0) return true;       // (a plan with one tiling: the other one is never launched)
+    return D.packed_lanes == sbk::kLanePackLanes && D.n_packed_tiles == (int64_t)D.n_tiles &&
+           D.rounds_dwords <= ((sbk::kRegRoundsNarrow + 3) & ~3);      // (rounds_dwords: the tiling's longest program, padded to 4)
+}
+inline bool use_lean_coded(const TilingScalars &T0, const TilingScalars &T1, const PrevCodeInputs &in) {
+    if (!use_prev_codes(T0, T1, in) || !sbk::kLanePackDecodable) return false;
+    return tiling_all_lane_packed(T0) && tiling_all_lane_packed(T1);
+}
+// LDS of a lean launch: positions, the palette, the 16 spare bytes -- no round words, no window (the tiling's lds_bytes holds both)
+inline size_t lean_lds_bytes(const TilingScalars &D) { return (size_t)D.max_local * sizeof(float4) + (size_t)D.pal_dwords * 4 + 16; }
+
 }  // namespace sbt

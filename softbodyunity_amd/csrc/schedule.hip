@@ -205,9 +205,11 @@ void halo_exchange(sb_solver *s, int slot, hipStream_t st) {
 }
 
 // The one place that launches tile_kernel: the block size IS the kernel's THREADS.
-template <int KIND, bool Q, int THREADS, int PPT, bool W, int G, bool C = false>
+template <int KIND, bool Q, int THREADS, int PPT, bool W, int G, bool C = false, int LEAN = sbk::kLeanOff>
 void launch_tile_kernel(const sb_solver *s, const DevTiling &D, const sbk::TileDesc *tiles_at_base, int n_wg, const sbk::TileArgs &A) {
-    hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, THREADS, PPT, W, G, C>), dim3(n_wg), dim3(THREADS), D.lds_bytes + s->lds_pad, s->stream, tiles_at_base, n_wg, A);
+    // (a lean launch stages neither round words nor a window: it asks for the LDS it carves, not for the tiling's)
+    const size_t lds = LEAN != sbk::kLeanOff ? sbt::lean_lds_bytes(D) : D.lds_bytes;
+    hipLaunchKernelGGL((sbk::tile_kernel<KIND, Q, THREADS, PPT, W, G, C, LEAN>), dim3(n_wg), dim3(THREADS), lds + s->lds_pad, s->stream, tiles_at_base, n_wg, A);
 }
 // From the shape (launch_shape.hpp) to the instantiation. 512 x 2 is built for tiles with tets / hinges only; a shape without a kernel is an error.
 template <int KIND, bool Q, bool W, int G>
@@ -253,6 +255,13 @@ void launch_tile(sb_solver *s, DevTiling &D, int tile_begin = 0, int tile_end = 
     if constexpr (sbk::kind_touches_prev(KIND)) if (s->prev_codes) {
         if (ghosts || sh.quads || !W || !sbt::same_width(sh, sbt::kShapeNarrow)) throw std::runtime_error("internal: previous-position codes are on, but the launch is not 128 x 4 spring-only with palette masses");
         A.prev_code = s->d_prev_code.p;
+        // every device tile lane-packed (decided with the codes, launch_shape.hpp use_lean_coded): the lean kernels, for every launch of the tick
+        if (s->lean_coded) {
+            constexpr sbt::LaunchShape N = sbt::kShapeNarrow;
+            // (kinematic targets belong to pinned particles: a launch that applies them has more than one inverse mass, or moves nothing)
+            if constexpr (!sbk::kind_is_kinematic(KIND)) if (s->w_uniform && sbk::kLeanUniformMass) return launch_tile_kernel<KIND, false, N.threads, N.ppt, true, sbk::kHaloNone, true, sbk::kLeanUniform>(s, D, tiles_at_base, n_wg, A);
+            return launch_tile_kernel<KIND, false, N.threads, N.ppt, true, sbk::kHaloNone, true, sbk::kLeanPalette>(s, D, tiles_at_base, n_wg, A);
+        }
         return launch_tile_kernel<KIND, false, sbt::kShapeNarrow.threads, sbt::kShapeNarrow.ppt, true, sbk::kHaloNone, true>(s, D, tiles_at_base, n_wg, A);
     }
     if (ghosts) {

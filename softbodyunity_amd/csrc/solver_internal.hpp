@@ -197,6 +197,7 @@ struct sb_solver {
     // Previous positions as 8-byte codes against x (prev_code.hpp), decided once at sb_finalize (launch_shape.hpp use_prev_codes): the tile
     // kernels then hand d_prev_code to each other and d_prev holds only the particles whose code does not fit. Nothing else reads either.
     bool prev_codes = false;
+    bool lean_coded = false;         // ... and every tile of both tilings is lane-packed: the coded launches run the lean kernels (launch_shape.hpp use_lean_coded)
     DevBuf<uint2> d_prev_code;       // one per local particle
     DevBuf<sbk::TickParams> d_tp;
     DevBuf<float> d_sendbuf, d_recvbuf;   // 3 (slot 1: 6) floats per ghost, peers back to back

@@ -166,6 +166,7 @@ void build_device(sb_solver *s) {
     for (const auto &D : s->halos) if (D->active()) ++pc.halo_slots;
     pc.steps_between_tiles = (int)s->t2_layer_range.size() + (int)s->gcolours.size();
     s->prev_codes = sbt::use_prev_codes(s->tiling[0], s->tiling[1], pc);
+    s->lean_coded = sbt::use_lean_coded(s->tiling[0], s->tiling[1], pc);
     if (s->prev_codes) {
         s->d_prev_code.alloc((size_t)s->n_local, s->dev_bytes);
         HIP_CHECK(hipMemset(s->d_prev_code.p, 0, (size_t)s->n_local * sizeof(uint2)));

@@ -42,13 +42,19 @@ template <bool QUADS, int THREADS> constexpr int kWavesPerSimd = QUADS ? (THREAD
 // them once x has arrived, MARK keeps the new previous position in the registers of the old one, the final store encodes it against the x
 // it writes. A particle whose code does not fit sets the escape bit and uses A.prev as before. The first kernel only writes codes, the last
 // one only reads them; the host launches either coded kernels in every tile launch of a solver or in none (launch_shape.hpp use_prev_codes).
-template <int KIND_, bool QUADS, int THREADS, int PPT, bool WPAL, int HALO = kHaloNone, bool CODED = false>
+// LEAN (kernel_types.hpp kLean*) = the coded kernel of a solver whose every device tile is lane-packed and dictionary-coded (launch_shape.hpp
+// use_lean_coded): the register-resident engine alone. No window and no second sweep of it, no round words in LDS, no wave items; the LDS
+// holds positions, palette and the spare 16 bytes. kLeanUniform: one inverse mass for the whole launch, read once as a scalar.
+template <int KIND_, bool QUADS, int THREADS, int PPT, bool WPAL, int HALO = kHaloNone, bool CODED = false, int LEAN = kLeanOff>
 // (kKindMidKinematic -- one launch per tick, and only when kinematic targets are pending -- gets one wave per SIMD less: its MARK step holds more
 // live values, and under the ordinary bound it spilled 4 .. 14 registers)
 __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ == 5 && !QUADS ? 1 : 0))) void tile_kernel(const TileDesc *tiles_at_base, int n_workgroups, TileArgs A) {
     // kKindMidKinematic = kKindMid whose MARK step also applies pending kinematic targets (see TileArgs::kin_map): an instantiation of its own, so the
     // ordinary mid-tick kernel carries nothing of it
     // (convention below: the predicates of kernel_types.hpp take KIND_ as it came; a comparison with one kind uses the folded KIND)
+    // the lean kernels are built for the one configuration launch_tile gives them (launch_shape.hpp use_lean_coded); they have no peek store
+    static_assert(LEAN == kLeanOff || (CODED && WPAL && !QUADS && THREADS == kLanePackLanes && HALO == kHaloNone && !kind_writes_peek(KIND_) && kind_touches_prev(KIND_)),
+                  "LEAN: coded 128-lane spring-only launches with palette masses, no ghosts, no peek");
     constexpr int KIND = kind_base(KIND_);
     constexpr bool KIN = kind_is_kinematic(KIND_);
     constexpr bool GHOSTS = HALO == kHaloGhosts;
@@ -60,9 +66,9 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     extern __shared__ uint4 lds_raw[];
     float4 *lds_pos = reinterpret_cast<float4 *>(lds_raw);
     uint32_t *s_rounds = reinterpret_cast<uint32_t *>(lds_pos + A.max_local);
-    float *s_pal = reinterpret_cast<float *>(s_rounds + A.rounds_dwords);
+    float *s_pal = reinterpret_cast<float *>(s_rounds + (LEAN ? 0 : A.rounds_dwords));
     uint32_t *cbuf = s_rounds + A.rounds_dwords + A.pal_dwords;
-    f32x3 *lds_spare = reinterpret_cast<f32x3 *>(cbuf + A.win_dwords);   // 16 bytes nobody reads (see the rounds)
+    f32x3 *lds_spare = reinterpret_cast<f32x3 *>(LEAN ? s_rounds + A.pal_dwords : cbuf + A.win_dwords);   // 16 bytes nobody reads (see the rounds)
     // the tile tables are never written by a kernel: read the descriptor through the constant address space so it
     // stays on the scalar-memory path (s_load), one wide read
     typedef const TileDesc __attribute__((address_space(4))) *ConstTileDescPtr;
@@ -153,7 +159,9 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     float pvx[PPT], pvy[PPT], pvz[PPT];
     uint32_t wi[PPT];
     uint32_t pc_lo[PPT], pc_hi[PPT];      // CODED: the particle's code as loaded
-    const int mypal = WPAL ? __float_as_int(A.wpal[tid & (kMaxMassPalette - 1)]) : 0;   // lane l holds palette entry l
+    constexpr bool kUniformW = LEAN == kLeanUniform;      // (tables_host.cpp build_state: one distinct inverse mass is palette entry 0)
+    const int mypal = WPAL && !kUniformW ? __float_as_int(A.wpal[tid & (kMaxMassPalette - 1)]) : 0;   // lane l holds palette entry l
+    const float w_launch = kUniformW ? A.wpal[0] : 0.0f;
 #pragma unroll
     for (int m = 0; m < PPT; ++m) {
         const int gc = max(g[m], 0);
@@ -161,7 +169,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
         const bool ghost = GHOSTS && gc >= A.n_owned;
         const float *px = ghost ? A.ghost_src + 6 * (size_t)(gc - A.n_owned) : A.pos.xyz + 3 * (size_t)gc;
         X[m].x = px[0]; X[m].y = px[1]; X[m].z = px[2];
-        if (WPAL) { wi[m] = A.w8[A.w_uniform ? 0 : gc]; X[m].w = 0.0f; } else { wi[m] = 0; X[m].w = A.pos.w[gc]; }
+        if (kUniformW) { wi[m] = 0; X[m].w = w_launch; }
+        else if (WPAL) { wi[m] = A.w8[A.w_uniform ? 0 : gc]; X[m].w = 0.0f; } else { wi[m] = 0; X[m].w = A.pos.w[gc]; }
         pvx[m] = pvy[m] = pvz[m] = 0.0f;
         pc_lo[m] = pc_hi[m] = 0u;
         if (kind_reads_prev(KIND_)) {
@@ -173,7 +182,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
         }
     }
     const bool rounds_in_lds = n_rounds_all <= A.rounds_dwords;
-    const uint32_t rw = tstream[max(min(tid, n_rounds_all - 1), 0)];        // (an empty program still has a 16-byte header)
+    const uint32_t rw = LEAN ? 0u : tstream[max(min(tid, n_rounds_all - 1), 0)];        // (an empty program still has a 16-byte header)
     // programs of at most 64 rounds: every wave also keeps round word `lane` in a register and reads it back with
     // v_readlane (no LDS round trip at the head of each round): +3 % at 64^3, +1 % at 256^3
     const bool rounds_in_lanes = n_rounds_all <= 64;
@@ -193,8 +202,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #ifndef SB_KW
 #define SB_KW (QUADS ? 4 : 2)
 #endif
-    constexpr int kW = SB_KW;
-    const bool lane_packed = !QUADS && kTileThreads == kLanePackLanes && td.packed_lanes == (uint32_t)kLanePackLanes;     // (uniform)
+    constexpr int kW = LEAN ? 1 : SB_KW;     // (LEAN: the lane's own 16-byte word is the whole sweep)
+    const bool lane_packed = LEAN ? true : !QUADS && kTileThreads == kLanePackLanes && td.packed_lanes == (uint32_t)kLanePackLanes;     // (uniform)
     const bool lane_packed_full = !WPAL && lane_packed && td.n_pal == 0;       // per-spring rest lengths behind the index words
     // 256-lane workgroups: one 8-byte word per lane (kWidePack*), loaded by the lane itself below
     const bool wide_packed = !QUADS && kTileThreads == kWidePackLanes && td.packed_lanes == (uint32_t)kWidePackLanes;       // (uniform)
@@ -203,7 +212,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     const uint32_t n4_first = wide_packed ? 0u : lane_packed ? (lane_packed_full ? 2u * (uint32_t)kLanePackLanes : (uint32_t)kLanePackLanes)
                                           : (min(win_lo + win, d_hi) - win_lo) >> 2;
     const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(tstream + win_lo);
-    u32x4 wv[kW];
+    u32x4 wv[kW < 2 ? 2 : kW];      // (LEAN sweeps once; the second element exists so that the full-slot read of wv[1] below, dead under WPAL, compiles)
 #pragma unroll
     for (int q = 0; q < kW; ++q) {
         const uint32_t i = tid + q * kTileThreads;
@@ -222,10 +231,11 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     // first and a single wait follows (left alone it emits load, wait, LDS write, load, wait, ... to save registers).
 #pragma unroll
     for (int m = 0; m < PPT; ++m) {
-        if (CODED) asm volatile("" ::"v"(X[m].x), "v"(pc_lo[m]), "v"(wi[m]), "v"(X[m].w));
+        if (kUniformW) asm volatile("" ::"v"(X[m].x), "v"(pc_lo[m]));
+        else if (CODED) asm volatile("" ::"v"(X[m].x), "v"(pc_lo[m]), "v"(wi[m]), "v"(X[m].w));
         else asm volatile("" ::"v"(X[m].x), "v"(pvx[m]), "v"(wi[m]), "v"(X[m].w));
     }
-    asm volatile("" ::"v"(mypal));
+    if (!kUniformW) asm volatile("" ::"v"(mypal));
     if (CODED && kind_reads_prev(KIND_)) {
         // x is here: decode. An escaped particle's previous position comes from the full-width array, one more dependent load, behind a
         // wave-uniform test (most waves hold no escape at all); its wait falls in front of MARK, behind the first pass of rounds.
@@ -245,22 +255,23 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
                 }
         }
     }
-    if (WPAL) {
+    if (WPAL && !kUniformW) {
 #pragma unroll
         for (int m = 0; m < PPT; ++m) X[m].w = __int_as_float(__builtin_amdgcn_ds_bpermute((int)(wi[m] << 2), mypal));
     }
 #pragma unroll
     for (int q = 0; q < kW; ++q) asm volatile("" ::"v"(wv[q].x));
-    asm volatile("" ::"v"(rw), "v"(palw), "v"(rwl), "v"(itreg));
+    if (LEAN) asm volatile("" ::"v"(palw), "v"(rwl));
+    else asm volatile("" ::"v"(rw), "v"(palw), "v"(rwl), "v"(itreg));
     if (!QUADS && kTileThreads == kWidePackLanes) asm volatile("" ::"v"(wp.x));
 #pragma unroll
     for (int m = 0; m < PPT; ++m)
         if (g[m] >= 0) *reinterpret_cast<f32x4 *>(lds_pos + tid + m * kTileThreads) = X[m];
-    if (rounds_in_lds && tid < n_rounds_all) s_rounds[tid] = rw;
+    if (!LEAN && rounds_in_lds && tid < n_rounds_all) s_rounds[tid] = rw;
     if (tid < n_pal) s_pal[tid] = __uint_as_float(palw);
     if (kTileThreads < kMaxRoundsLds && rounds_in_lds)
         for (int q = tid + kTileThreads; q < n_rounds_all; q += kTileThreads) s_rounds[q] = tstream[q];
-    if (kTileThreads < kMaxPalette)
+    if (!LEAN && kTileThreads < kMaxPalette)      // (a lane-packed tile's palette: at most kLanePackMaxPalette entries)
         for (int q = tid + kTileThreads; q < n_pal; q += kTileThreads) s_pal[q] = __uint_as_float(tstream[((n_rounds_all + 3) & ~3) + q]);
     {
         u32x4 *dst = reinterpret_cast<u32x4 *>(cbuf);
@@ -278,7 +289,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     if (!WPAL && !QUADS && kTileThreads == kLanePackLanes && lane_packed_full)
         wc = *reinterpret_cast<const u32x2 *>(tstream + win_lo + 8u * (uint32_t)kLanePackLanes + 2u * (uint32_t)tid);
 #if defined(SB_ABLATE) && SB_ABLATE == 5   // timing experiment only: dispatch + descriptor + every load of the tile, nothing else
-    if (n_local >= 0) { if (lds_pos[tid].x == 1.2345e-30f && cbuf[tid] == 0x12345678u) A.vel[0] = tp.h; return; }
+    if (n_local >= 0) { if (lds_pos[tid].x == 1.2345e-30f && (LEAN ? wv[0].x : cbuf[tid]) == 0x12345678u) A.vel[0] = tp.h; return; }
 #endif
 
     // MARK step (SPEC.md §2): collide + velocity update of the substep that just finished, integrate of the next one
@@ -288,6 +299,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
             if (g[m] >= 0) {
                 const int l = tid + m * kTileThreads;
                 float4 P = lds_pos[l];
+                if constexpr (kUniformW) P.w = w_launch;
                 if (KIND != kKindFirst && tp.plane_on && P.w > 0.0f) {   // collide: end of the substep that just finished
                     float a = tp.pnx * P.x, b = tp.pny * P.y, c = tp.pnz * P.z;
                     float pen = ((a + b) + c) - tp.pd;
@@ -339,8 +351,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
     constexpr int kRegRounds = THREADS >= 256 ? kRegRoundsWide : kRegRoundsNarrow;       // (kernel_types.hpp: the host packs lanes by the same constants)
     // (round 3: also for tiles whose slots are NOT dictionary-coded -- per-spring rest lengths, {i | j<<16, rest} pairs: the same 2
     // registers per constraint, only the decode differs -- so that a mesh with varied rest lengths keeps the short path)
-    if (kRegRounds > 0 && !QUADS && n_rounds_all <= kRegRounds && n_rounds_all > 0 && (kRegFullSlots || n_pal > 0) && (any_packed || d_hi - d_lo <= win)) {
-        const bool tile_compact = n_pal > 0;      // (uniform per tile: build_device codes all of a tile's groups one way)
+    if (LEAN || (kRegRounds > 0 && !QUADS && n_rounds_all <= kRegRounds && n_rounds_all > 0 && (kRegFullSlots || n_pal > 0) && (any_packed || d_hi - d_lo <= win))) {
+        const bool tile_compact = LEAN ? true : n_pal > 0;      // (uniform per tile: build_device codes all of a tile's groups one way)
         uint32_t rs[kRegRounds > 0 ? kRegRounds : 1][kCPL];
         float rl[kRegRounds > 0 ? kRegRounds : 1][kCPL];
         int rcnt[kRegRounds > 0 ? kRegRounds : 1];
@@ -421,6 +433,8 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #pragma unroll
                 for (int u = 0; u < kCPL; ++u) {
                     float4 a = make_float4(ca[u].x, ca[u].y, ca[u].z, ca[u].w), b = make_float4(cb[u].x, cb[u].y, cb[u].z, cb[u].w);
+                    // (one inverse mass for the launch: the same value as the LDS holds, so the same bits, as a scalar)
+                    if constexpr (kUniformW) { a.w = w_launch; b.w = w_launch; }
                     con[u] = project_distance_nobranch(a, b, L0[u], tp.at_d) && con[u];
                     ca[u].x = a.x; ca[u].y = a.y; ca[u].z = a.z; cb[u].x = b.x; cb[u].y = b.y; cb[u].z = b.z;
                 }
@@ -658,6 +672,7 @@ __global__ __launch_bounds__(THREADS, (kWavesPerSimd<QUADS, THREADS> - (KIND_ ==
 #endif
     }
     }
+    // ---- the final store: x, and (CODED, between two kernels of a tick) the previous position MARK left in registers as a code against that x ----
 #pragma unroll
     for (int m = 0; m < PPT; ++m)
         if (g[m] >= 0) {
