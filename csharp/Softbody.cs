@@ -4,6 +4,7 @@
 // FixedUpdate() -> sb_group_step(Time.fixedDeltaTime, substeps) + sb_group_get_positions                     (one tick, SPEC.md §2)
 //                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
 //                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
+//                  colliders: sb_group_collide before the step -- the scene's SphereCollider / CapsuleCollider / BoxCollider list in world space, moving with their Rigidbody or transform (SPEC.md 2f)
 // Teleport() / Respawn() -> sb_group_place: the body follows a requested position and rotation, or starts over from its rest pose (SPEC.md 2d)
 // OnDestroy()   -> sb_group_destroy
 //
@@ -48,6 +49,13 @@ namespace SoftbodyMI355X
         public float airDragTangential = 0f;
         [Tooltip("Pressure along the winding's outward normal, per unit area: inflates a closed skin (negative deflates).")]
         public float internalPressure = 0f;
+        [Header("Scene colliders (SPEC.md 2f: contacts resolved before every tick; an empty list = off)")]
+        [Tooltip("SphereCollider, CapsuleCollider and BoxCollider components the body rests on, slides off and is shoved by, in this order. Other collider types and null entries are skipped. Particles collide, not triangles: a collider thinner than the particle spacing passes between them. Nothing acts back on the collider.")]
+        public Collider[] colliders = new Collider[0];
+        [Tooltip("Coulomb friction of the body against every collider (>= 0).")]
+        public float friction = 0.5f;
+        [Tooltip("Restitution of the body against every collider (0 .. 1).")]
+        public float bounciness = 0f;
         [Header("Device")]
         [SerializeField] bool useGpu = true;
         [Tooltip("First HIP device ordinal; with deviceCount > 1 the body is split spatially over devices device .. device + deviceCount - 1.")]
@@ -236,6 +244,7 @@ namespace SoftbodyMI355X
         {
             SendImpulses();      // everything queued since the last tick, in one call, before the step
             ApplySurfaceForces();      // wind, air drag, pressure: on the velocities the impulses left, before the step
+            SendColliders();           // contacts with the scene's colliders: on the state all of that left, before the step
             bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
             {
@@ -532,6 +541,147 @@ namespace SoftbodyMI355X
                                          pressure = internalPressure, dt = Time.fixedDeltaTime };
             if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_apply_surface_forces(handle, ref f), "sb_group_apply_surface_forces");
             else if (cpu != null) cpu.ApplySurfaceForces(f, renderTriangles);
+        }
+
+        // ---- scene colliders (SPEC.md 2f) ----
+        SbCollider[] colliderRecords = new SbCollider[0];
+        Vector3[] colliderLastPosition = new Vector3[0];
+        Quaternion[] colliderLastRotation = new Quaternion[0];
+        Collider[] colliderLastSeen = new Collider[0];
+
+        /// <summary>The inspector list `colliders`, converted to simulation space -- the collider's transform with its scale, then the body's frame --
+        /// and sent in ONE sb_group_collide call before the step (SPEC.md 2f): nothing is sent while the list is empty, so a body that touches
+        /// nothing keeps its fused ticks. A collider's velocity comes from its attached Rigidbody, else from its transform's change since the
+        /// last FixedUpdate (none on the first one it is seen). Unity's rules for scale: a sphere's radius by the largest axis, a capsule's
+        /// radius by the largest axis across its direction and its height by the axis along it, a box's size by each axis. CPU branch: the
+        /// same section 2f on the arrays the C# solver steps.</summary>
+        void SendColliders()
+        {
+            if (colliders == null || colliders.Length == 0) return;
+            int m = colliders.Length;
+            if (colliderRecords.Length != m)
+            {
+                colliderRecords = new SbCollider[m]; colliderLastPosition = new Vector3[m]; colliderLastRotation = new Quaternion[m]; colliderLastSeen = new Collider[m];
+            }
+            float dt = Time.fixedDeltaTime;
+            Quaternion toSim = Quaternion.Inverse(FrameRotation());
+            float simPerWorld = WorldToSimVector(Vector3.right).magnitude;      // (the body's transform is expected to be scaled uniformly)
+            int count = 0;
+            for (int i = 0; i < m; ++i)
+            {
+                Collider c = colliders[i];
+                if (c == null || !c.enabled || !c.gameObject.activeInHierarchy) { colliderLastSeen[i] = null; continue; }
+                Transform t = c.transform;
+                Vector3 s = t.lossyScale; s = new Vector3(Mathf.Abs(s.x), Mathf.Abs(s.y), Mathf.Abs(s.z));
+                var r = new SbCollider { friction = Mathf.Max(0f, friction), restitution = Mathf.Clamp01(bounciness), rot00 = 1f, rot11 = 1f, rot22 = 1f };
+                Vector3 a;
+                if (c is SphereCollider sc)
+                {
+                    r.shape = SoftbodyNative.SB_COLLIDER_SPHERE;
+                    a = t.TransformPoint(sc.center);
+                    r.radius = sc.radius * Mathf.Max(s.x, Mathf.Max(s.y, s.z)) * simPerWorld;
+                }
+                else if (c is CapsuleCollider cc)
+                {
+                    r.shape = SoftbodyNative.SB_COLLIDER_CAPSULE;
+                    int d = cc.direction;                                      // 0, 1, 2 = the local x, y, z axis
+                    float along = d == 0 ? s.x : (d == 1 ? s.y : s.z);
+                    float across = d == 0 ? Mathf.Max(s.y, s.z) : (d == 1 ? Mathf.Max(s.x, s.z) : Mathf.Max(s.x, s.y));
+                    float radius = cc.radius * across;
+                    float half = Mathf.Max(0f, 0.5f * cc.height * along - radius);      // from the centre to the centre of an end's half sphere
+                    Vector3 axis = t.rotation * (d == 0 ? Vector3.right : (d == 1 ? Vector3.up : Vector3.forward));
+                    Vector3 mid = t.TransformPoint(cc.center);
+                    a = mid - half * axis;
+                    Vector3 b = WorldToSimPoint(mid + half * axis);
+                    r.bX = b.x; r.bY = b.y; r.bZ = b.z;
+                    r.radius = radius * simPerWorld;
+                }
+                else if (c is BoxCollider bc)
+                {
+                    r.shape = SoftbodyNative.SB_COLLIDER_BOX;
+                    a = t.TransformPoint(bc.center);
+                    Vector3 ax = toSim * (t.rotation * Vector3.right), ay = toSim * (t.rotation * Vector3.up), az = toSim * (t.rotation * Vector3.forward);
+                    r.rot00 = ax.x; r.rot01 = ax.y; r.rot02 = ax.z; r.rot10 = ay.x; r.rot11 = ay.y; r.rot12 = ay.z; r.rot20 = az.x; r.rot21 = az.y; r.rot22 = az.z;
+                    r.halfX = 0.5f * Mathf.Abs(bc.size.x) * s.x * simPerWorld; r.halfY = 0.5f * Mathf.Abs(bc.size.y) * s.y * simPerWorld; r.halfZ = 0.5f * Mathf.Abs(bc.size.z) * s.z * simPerWorld;
+                }
+                else { colliderLastSeen[i] = null; continue; }                   // (MeshCollider, TerrainCollider, ...: not among SPEC.md 2f's shapes)
+                // the velocity of the collider's point a and its angular velocity, world space
+                Vector3 lin = Vector3.zero, ang = Vector3.zero;
+                Rigidbody rb = c.attachedRigidbody;
+                if (rb != null) { lin = rb.GetPointVelocity(a); ang = rb.angularVelocity; }
+                else if (colliderLastSeen[i] == c && dt > 0f)
+                {
+                    (t.rotation * Quaternion.Inverse(colliderLastRotation[i])).ToAngleAxis(out float angle, out Vector3 axis);
+                    if (angle > 180f) angle -= 360f;
+                    if (IsFinite(axis)) ang = axis * (angle * Mathf.Deg2Rad / dt);
+                    lin = (a - colliderLastPosition[i]) / dt;
+                }
+                colliderLastSeen[i] = c; colliderLastPosition[i] = a; colliderLastRotation[i] = t.rotation;
+                Vector3 aSim = WorldToSimPoint(a), linSim = WorldToSimVector(lin), angSim = toSim * ang;
+                r.aX = aSim.x; r.aY = aSim.y; r.aZ = aSim.z;
+                r.linX = linSim.x; r.linY = linSim.y; r.linZ = linSim.z; r.angX = angSim.x; r.angY = angSim.y; r.angZ = angSim.z;
+                colliderRecords[count++] = r;
+            }
+            if (count == 0) return;
+            bodyHas = 0;
+            if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide(handle, colliderRecords, count), "sb_group_collide");
+            else for (int k = 0; k < count; ++k) CollideCpu(colliderRecords[k]);
+        }
+
+        static bool RoundRule(Vector3 x, Vector3 c, float radius, out Vector3 n, out float depth)
+        {
+            Vector3 d = x - c;
+            float r2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+            n = Vector3.up; depth = 0f;
+            if (!(r2 < radius * radius)) return false;
+            float r = Mathf.Sqrt(r2);
+            if (r2 != 0f) n = d / r;
+            depth = radius - r;
+            return true;
+        }
+
+        /// <summary>SPEC.md 2f for one collider on the CPU branch's arrays (the order of operations follows the section; C# gives no guarantee
+        /// against a fused multiply-add, so this branch is not bit for bit the plugin).</summary>
+        void CollideCpu(SbCollider c)
+        {
+            Vector3 a = new Vector3(c.aX, c.aY, c.aZ), b = new Vector3(c.bX, c.bY, c.bZ), lin = new Vector3(c.linX, c.linY, c.linZ), ang = new Vector3(c.angX, c.angY, c.angZ);
+            Vector3[] axes = { new Vector3(c.rot00, c.rot01, c.rot02), new Vector3(c.rot10, c.rot11, c.rot12), new Vector3(c.rot20, c.rot21, c.rot22) };
+            float[] half = { c.halfX, c.halfY, c.halfZ };
+            for (int i = 0; i < positions.Length; ++i)
+            {
+                if (!(inverseMass[i] > 0f)) continue;
+                Vector3 x = positions[i], n; float depth;
+                if (c.shape == SoftbodyNative.SB_COLLIDER_SPHERE) { if (!RoundRule(x, a, c.radius, out n, out depth)) continue; }
+                else if (c.shape == SoftbodyNative.SB_COLLIDER_CAPSULE)
+                {
+                    Vector3 ab = b - a;
+                    float L2 = Vector3.Dot(ab, ab), t = Vector3.Dot(x - a, ab) / L2;
+                    if (L2 == 0f || float.IsNaN(t)) t = 0f;
+                    t = t < 0f ? 0f : (t > 1f ? 1f : t);
+                    if (!RoundRule(x, a + t * ab, c.radius, out n, out depth)) continue;
+                }
+                else
+                {
+                    Vector3 e = x - a;
+                    float q0 = Vector3.Dot(e, axes[0]), q1 = Vector3.Dot(e, axes[1]), q2 = Vector3.Dot(e, axes[2]);
+                    if (!(Mathf.Abs(q0) < half[0] && Mathf.Abs(q1) < half[1] && Mathf.Abs(q2) < half[2])) continue;
+                    float d0 = half[0] - Mathf.Abs(q0), d1 = half[1] - Mathf.Abs(q1), d2 = half[2] - Mathf.Abs(q2);
+                    int k = 0; depth = d0; float q = q0;
+                    if (d1 < depth) { k = 1; depth = d1; q = q1; }
+                    if (d2 < depth) { k = 2; depth = d2; q = q2; }
+                    n = q < 0f ? -axes[k] : axes[k];
+                }
+                x += depth * n;
+                positions[i] = x;
+                Vector3 vc = lin + Vector3.Cross(ang, x - a), u = velocities[i] - vc;
+                float un = Vector3.Dot(u, n);
+                if (!(un < 0f)) continue;                                      // separating: the velocity stays
+                float jn = -un;
+                Vector3 ut = u - un * n;
+                float t2 = Vector3.Dot(ut, ut), tl = Mathf.Sqrt(t2), lim = c.friction * jn;
+                ut = (t2 > 0f && tl > lim) ? (1f - lim / tl) * ut : Vector3.zero;
+                velocities[i] = vc + (ut + (c.restitution * jn) * n);
+            }
         }
 
         /// <summary>transform.position / rotation = ... (Rigidbody.MovePosition + MoveRotation) for the soft body, between two ticks and on the GPUs

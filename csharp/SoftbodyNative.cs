@@ -195,6 +195,24 @@ namespace SoftbodyMI355X
         public float angX, angY, angZ;
     }
 
+    /// <summary>sb_collider (128 bytes): one entry of sb_group_collide's list (SPEC.md 2f). shape = SB_COLLIDER_*; a: the centre (SPHERE, BOX) or one
+    /// end of the segment a b (CAPSULE), and the pivot of ang; rot: the box's three world-space axes as rows, half its half extents along them; lin: the
+    /// collider's velocity at a, ang its angular velocity in radians per second; friction >= 0, restitution in [0, 1]; flags and reserved stay 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbCollider
+    {
+        public uint shape, flags;
+        public float aX, aY, aZ;
+        public float bX, bY, bZ;
+        public float rot00, rot01, rot02, rot10, rot11, rot12, rot20, rot21, rot22;
+        public float halfX, halfY, halfZ;
+        public float radius;
+        public float linX, linY, linZ;
+        public float angX, angY, angZ;
+        public float friction, restitution;
+        public int reserved0, reserved1, reserved2;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -224,6 +242,9 @@ namespace SoftbodyMI355X
 
         // sb_placement.flags (SPEC.md 2d), named as in include/softbody_group.h
         public const uint SB_PLACE_FROM_REFERENCE = 1, SB_PLACE_SET_VELOCITY = 2, SB_PLACE_KEEP_PINNED = 4;
+
+        // sb_collider.shape (SPEC.md 2f), named as in include/softbody_group.h
+        public const uint SB_COLLIDER_SPHERE = 0, SB_COLLIDER_CAPSULE = 1, SB_COLLIDER_BOX = 2;
 
         [DllImport(Lib, CallingConvention = CC)] public static extern void sb_desc_default(ref SbDesc d);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_create(ref SbDesc desc, out IntPtr solver);
@@ -332,6 +353,7 @@ namespace SoftbodyMI355X
         // queries: 4 floats each = x, y, z, max_distance (SPEC.md 6g)
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_closest_points(IntPtr g, float[] queries, int count, [Out] SbClosestHit[] hits);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_place(IntPtr g, ref SbPlacement placement);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide(IntPtr g, SbCollider[] colliders, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);

@@ -244,6 +244,44 @@ typedef struct {
  * of every particle a rank holds (12 bytes each); until then sb_stats.device_bytes is what it was. Both host models. */
 int sb_group_place(sb_group *g, const sb_placement *p);
 
+/* ---- collider contacts: spheres, capsules and boxes between two ticks (SPEC.md 2f) ------------------------------------------------------- */
+/* What a scene's SphereCollider, CapsuleCollider and BoxCollider are to a rigid body: the body rests on them, slides off them and is shoved
+ * by them. ONE streaming pass per rank over every particle it holds, ghosts included (the same arithmetic on a ghost gives its owner's
+ * bits: no exchange), instead of a closest-point query, a penetration test and a SURFACE impulse per collider and frame. Per particle with
+ * inverse mass > 0 the list is walked in order -- the position and velocity after collider k are the input of collider k + 1 -- in binary32
+ * without FMA (SPEC.md 2f has the parentheses):
+ *     SPHERE  (a, radius)        hit iff |x - a|^2 < radius^2;      n = (x - a) / |x - a| ((0, 1, 0) at the centre), depth = radius - |x - a|
+ *     CAPSULE (a, b, radius)     the sphere's rule about the closest point of the segment a b
+ *     BOX     (a, rot, half)     q_k = (x - a) . rot[3k..3k+2]; hit iff |q_k| < half[k] for k = 0, 1, 2; the exit face is the one with the
+ *                                smallest half[k] - |q_k| (ties: the lowest k), n = +-row k. rot: three orthonormal world-space axes, not checked
+ *     x' = x + depth n           vc = lin + ang x (x' - a), u = v - vc, un = u . n
+ *     un < 0 (approaching):      v' = vc + (ut' + restitution (-un) n), ut' the tangential part of u shortened by friction (-un) (Coulomb;
+ *                                removed when shorter than that: stick). Otherwise the velocity is not written.
+ * A particle with inverse mass 0 is left entirely alone, and a particle that no collider touches keeps every bit of its position and
+ * velocity: a call that touches nothing changes nothing. A NaN or infinite position is never hit. A written component that comes out NaN
+ * is stored as 0x7fc00000. Contacts are resolved once per call (per tick, not per substep); particles collide, not triangles (a collider
+ * thinner than the particle spacing passes between them); nothing acts back on the collider; there is no self-collision. Asynchronous;
+ * completes every rank's held-back last kernel first, as sb_group_place does, which lands pending kinematic targets; the next tick starts
+ * unfused. The ground plane, the render snapshot delivered last, the render device and a render embedding take no part. */
+#define SB_COLLIDER_SPHERE  0u
+#define SB_COLLIDER_CAPSULE 1u
+#define SB_COLLIDER_BOX     2u
+typedef struct {
+    uint32_t shape, flags;         /* SB_COLLIDER_*; flags = 0 */
+    float a[3], b[3];              /* SPHERE: centre a. CAPSULE: segment a b. BOX: centre a. a is also the pivot of ang */
+    float rot[9], half[3];         /* BOX: the axes as rows, the half extents along them */
+    float radius;                  /* SPHERE, CAPSULE */
+    float lin[3], ang[3];          /* the collider's velocity at a and its angular velocity (radians per second) */
+    float friction, restitution;   /* Coulomb coefficient >= 0; restitution in [0, 1] */
+    int32_t reserved[3];           /* 0 */
+} sb_collider;                     /* 128 bytes */
+/* count colliders in list order; calls apply in call order. count == 0 passes the checks and does nothing at all (the tick stays held
+ * back). SB_ERR_INVALID_ARG (null group, count < 0, null colliders with count > 0, an unknown shape, flags or a reserved word != 0, a NaN
+ * or infinite field -- of any shape's, used or not --, radius < 0, a negative half, friction < 0, restitution outside [0, 1]: all checked
+ * before the group is touched), SB_ERR_STATE before sb_group_finalize; a refused call changes nothing. The list is copied before the call
+ * returns. No device memory is allocated. Both host models, any number of ranks. */
+int sb_group_collide(sb_group *g, const sb_collider *colliders, int32_t count);
+
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);
 int32_t sb_group_rank_count(const sb_group *g);

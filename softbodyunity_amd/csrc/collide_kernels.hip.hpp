@@ -1,0 +1,221 @@
+// collide_kernels.hip.hpp — collider contacts between two ticks (SPEC.md 2f): one streaming pass that pushes every particle a rank holds out
+// of a list of spheres, capsules and boxes and gives it the contact's velocity response, in binary32 without FMA, in the order SPEC.md 2f
+// parenthesises. Included by collide.hip alone.
+#pragma once
+#include "device_math.hip.hpp"
+
+namespace sbk {
+
+// sb_collider as the kernel reads it (collide.hip asserts the two layouts equal): 128 bytes
+struct ColliderRec {
+    uint32_t shape, flags;
+    float a[3], b[3], rot[9], half[3], radius, lin[3], ang[3], friction, restitution;
+    int32_t reserved[3];
+};
+constexpr int kColliderBatch = 16;      // records per launch: 2 KiB of kernel arguments, read with scalar loads (uniform for the whole grid)
+struct ColliderBatch {
+    ColliderRec c[kColliderBatch];
+};
+constexpr uint32_t kColliderSphere = 0, kColliderCapsule = 1, kColliderBox = 2;      // SB_COLLIDER_*
+
+// SPEC.md 2f, the rule of 2c and 2d: a component that is WRITTEN and comes out NaN is stored as THE quiet NaN 0x7fc00000
+__device__ __forceinline__ uint32_t collide_canonical_bits(float v) { return v == v ? __float_as_uint(v) : 0x7fc00000u; }
+
+// The sphere's rule about the point (cx, cy, cz): hit, outward normal, depth
+__device__ __forceinline__ bool collide_round(float x, float y, float z, float cx, float cy, float cz, float radius, float (&n)[3], float &depth) {
+    const float dx = x - cx, dy = y - cy, dz = z - cz;
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float xy = xx + yy;
+    const float r2 = xy + zz;
+    const float rr = radius * radius;
+    if (!(r2 < rr)) return false;      // (a NaN or infinite position compares false)
+    const float r = sqrtf(r2);
+    const bool centre = r2 == 0.0f;
+    const float qx = dx / r, qy = dy / r, qz = dz / r;
+    n[0] = centre ? 0.0f : qx; n[1] = centre ? 1.0f : qy; n[2] = centre ? 0.0f : qz;
+    depth = radius - r;
+    return true;
+}
+
+// (hit, n, depth) of one point against one collider. The branch on C.shape is on a scalar: the record is uniform for the grid.
+__device__ __forceinline__ bool collide_shape(const ColliderRec &C, float x, float y, float z, float (&n)[3], float &depth) {
+    if (C.shape == kColliderSphere) return collide_round(x, y, z, C.a[0], C.a[1], C.a[2], C.radius, n, depth);
+    if (C.shape == kColliderCapsule) {
+        const float abx = C.b[0] - C.a[0], aby = C.b[1] - C.a[1], abz = C.b[2] - C.a[2];
+        const float lx = abx * abx, ly = aby * aby, lz = abz * abz;
+        const float lxy = lx + ly;
+        const float L2 = lxy + lz;
+        const float ex = x - C.a[0], ey = y - C.a[1], ez = z - C.a[2];
+        const float sx = ex * abx, sy = ey * aby, sz = ez * abz;
+        const float sxy = sx + sy;
+        const float s = sxy + sz;
+        float t = s / L2;
+        t = (L2 == 0.0f || t != t) ? 0.0f : t;
+        t = t < 0.0f ? 0.0f : t;
+        t = t > 1.0f ? 1.0f : t;
+        const float tx = t * abx, ty = t * aby, tz = t * abz;
+        const float cx = C.a[0] + tx, cy = C.a[1] + ty, cz = C.a[2] + tz;
+        return collide_round(x, y, z, cx, cy, cz, C.radius, n, depth);
+    }
+    const float ex = x - C.a[0], ey = y - C.a[1], ez = z - C.a[2];
+    float q[3], dep[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = ex * C.rot[3 * k], b = ey * C.rot[3 * k + 1], c = ez * C.rot[3 * k + 2];
+        const float ab = a + b;
+        q[k] = ab + c;
+        dep[k] = C.half[k] - __builtin_fabsf(q[k]);
+    }
+    if (!(__builtin_fabsf(q[0]) < C.half[0] && __builtin_fabsf(q[1]) < C.half[1] && __builtin_fabsf(q[2]) < C.half[2])) return false;
+    // the exit face: the smallest depth, a tie keeps the lowest k
+    const bool f1 = dep[1] < dep[0];
+    float d = f1 ? dep[1] : dep[0], qf = f1 ? q[1] : q[0];
+    float ax = f1 ? C.rot[3] : C.rot[0], ay = f1 ? C.rot[4] : C.rot[1], az = f1 ? C.rot[5] : C.rot[2];
+    const bool f2 = dep[2] < d;
+    d = f2 ? dep[2] : d; qf = f2 ? q[2] : qf;
+    ax = f2 ? C.rot[6] : ax; ay = f2 ? C.rot[7] : ay; az = f2 ? C.rot[8] : az;
+    const bool neg = qf < 0.0f;
+    n[0] = neg ? -ax : ax; n[1] = neg ? -ay : ay; n[2] = neg ? -az : az;
+    depth = d;
+    return true;
+}
+
+// The response of SPEC.md 2f for a particle that is hit. x: in and out (always written); v: in, and out when the function returns true
+// (the particle approaches the collider); a separating particle's velocity is not written and keeps its bits.
+__device__ __forceinline__ bool collide_respond(const ColliderRec &C, const float (&n)[3], float depth, uint32_t (&x)[3], uint32_t (&v)[3]) {
+    float xn[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float push = depth * n[c];
+        xn[c] = __uint_as_float(x[c]) + push;
+        x[c] = collide_canonical_bits(xn[c]);
+    }
+    const float px = xn[0] - C.a[0], py = xn[1] - C.a[1], pz = xn[2] - C.a[2];
+    const float yz = C.ang[1] * pz, zy = C.ang[2] * py;
+    const float zx = C.ang[2] * px, xz = C.ang[0] * pz;
+    const float xy = C.ang[0] * py, yx = C.ang[1] * px;
+    const float cx = yz - zy, cy = zx - xz, cz = xy - yx;
+    const float vc[3] = {C.lin[0] + cx, C.lin[1] + cy, C.lin[2] + cz};
+    const float ux = __uint_as_float(v[0]) - vc[0], uy = __uint_as_float(v[1]) - vc[1], uz = __uint_as_float(v[2]) - vc[2];
+    const float a = ux * n[0], b = uy * n[1], e = uz * n[2];
+    const float ab = a + b;
+    const float un = ab + e;
+    if (!(un < 0.0f)) return false;
+    const float jn = -un;
+    const float ox = un * n[0], oy = un * n[1], oz = un * n[2];
+    float t[3] = {ux - ox, uy - oy, uz - oz};
+    const float txx = t[0] * t[0], tyy = t[1] * t[1], tzz = t[2] * t[2];
+    const float txy = txx + tyy;
+    const float t2 = txy + tzz;
+    const float tl = sqrtf(t2);
+    const float lim = C.friction * jn;
+    const bool slip = t2 > 0.0f && tl > lim;
+    const float ratio = lim / tl;
+    const float scale = 1.0f - ratio;
+    const float un2 = C.restitution * jn;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float st = scale * t[c];
+        const float tc = slip ? st : 0.0f;
+        const float nc = un2 * n[c];
+        const float tn = tc + nc;
+        v[c] = collide_canonical_bits(vc[c] + tn);
+    }
+    return true;
+}
+
+// One aligned 16-byte store, as placement's (placement_kernels.hip.hpp has the reasons: the compiler re-splits a lane's 48 bytes into
+// 12-byte stores; the statement ends with the two wait states a store of more than 8 bytes needs before its data registers are reused).
+typedef uint32_t collide_u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void collide_store4(uint4 *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    const collide_u32x4_t v = {a, b, c, d};
+    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
+constexpr int kCollideLanes = 256, kCollidePerLane = 4;      // 1 024 particles per workgroup
+
+// place_kernel's access shape: a lane takes FOUR consecutive particles = three aligned 16-byte words of x and one of w; the last n mod 4
+// particles take one lane each, word by word. What differs is what is NOT moved: velocities are read only by a lane that has a hit (at
+// its first hit; they then stay in registers for the rest of the batch), and a lane stores only the 16-byte words of x and v that hold a
+// component of a particle some collider wrote -- an untouched body costs 12 + 4 bytes per particle, and untouched particles keep every
+// bit because nothing is written over them. The records of a batch are kernel arguments: scalar loads, one shape branch per collider on a
+// scalar register. Particles are carried in registers across the colliders of the batch (the position after collider k is the input of
+// collider k + 1). No LDS, no atomics: a lane writes only words it read.
+__global__ __launch_bounds__(kCollideLanes) void collide_kernel(float *pos, float *vel, const float *wf, int64_t n, int count, ColliderBatch B) {
+    const int64_t k = (int64_t)blockIdx.x * kCollideLanes + threadIdx.x;
+    const int64_t n4 = n / kCollidePerLane;
+    if (k < n4) {
+        uint4 *px = reinterpret_cast<uint4 *>(pos) + 3 * k, *pv = reinterpret_cast<uint4 *>(vel) + 3 * k;
+        const float4 W = reinterpret_cast<const float4 *>(wf)[k];
+        const float w[4] = {W.x, W.y, W.z, W.w};
+        if (!(W.x > 0.0f || W.y > 0.0f || W.z > 0.0f || W.w > 0.0f)) return;      // four pinned particles: nothing to read
+        uint32_t x[12], v[12] = {};
+        {
+            const uint4 a = px[0], b = px[1], c = px[2];
+            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w; x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
+        }
+        bool have_v = false;
+        unsigned wrote_x = 0, wrote_v = 0;      // bit j: particle j of the lane
+        for (int ci = 0; ci < count; ++ci) {
+            const ColliderRec &C = B.c[ci];
+            float nrm[4][3], depth[4];
+            bool hit[4];
+#pragma unroll
+            for (int j = 0; j < kCollidePerLane; ++j)
+                hit[j] = w[j] > 0.0f && collide_shape(C, __uint_as_float(x[3 * j]), __uint_as_float(x[3 * j + 1]), __uint_as_float(x[3 * j + 2]), nrm[j], depth[j]);
+            if (!(hit[0] || hit[1] || hit[2] || hit[3])) continue;
+            if (!have_v) {
+                const uint4 a = pv[0], b = pv[1], c = pv[2];
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w; v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+                have_v = true;
+            }
+#pragma unroll
+            for (int j = 0; j < kCollidePerLane; ++j) {
+                if (!hit[j]) continue;
+                uint32_t xj[3] = {x[3 * j], x[3 * j + 1], x[3 * j + 2]}, vj[3] = {v[3 * j], v[3 * j + 1], v[3 * j + 2]};
+                const bool wv = collide_respond(C, nrm[j], depth[j], xj, vj);
+                wrote_x |= 1u << j;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) x[3 * j + c] = xj[c];
+                if (wv) {
+                    wrote_v |= 1u << j;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[3 * j + c] = vj[c];
+                }
+            }
+        }
+        // word 0 holds particles 0 and 1 (floats 0..3), word 1 particles 1 and 2, word 2 particles 2 and 3
+        if (wrote_x & 0x3u) collide_store4(px, x[0], x[1], x[2], x[3]);
+        if (wrote_x & 0x6u) collide_store4(px + 1, x[4], x[5], x[6], x[7]);
+        if (wrote_x & 0xcu) collide_store4(px + 2, x[8], x[9], x[10], x[11]);
+        // (wrote_v != 0 implies have_v: every word of v stored here was read)
+        if (wrote_v & 0x3u) collide_store4(pv, v[0], v[1], v[2], v[3]);
+        if (wrote_v & 0x6u) collide_store4(pv + 1, v[4], v[5], v[6], v[7]);
+        if (wrote_v & 0xcu) collide_store4(pv + 2, v[8], v[9], v[10], v[11]);
+        return;
+    }
+    const int64_t p = n4 * kCollidePerLane + (k - n4);
+    if (p >= n) return;
+    const float w = wf[p];
+    if (!(w > 0.0f)) return;
+    uint32_t *xs = reinterpret_cast<uint32_t *>(pos) + 3 * p, *vs = reinterpret_cast<uint32_t *>(vel) + 3 * p;
+    uint32_t x[3] = {xs[0], xs[1], xs[2]}, v[3] = {};
+    bool have_v = false, wrote_x = false, wrote_v = false;
+    for (int ci = 0; ci < count; ++ci) {
+        const ColliderRec &C = B.c[ci];
+        float nrm[3], depth;
+        if (!collide_shape(C, __uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), nrm, depth)) continue;
+        if (!have_v) { v[0] = vs[0]; v[1] = vs[1]; v[2] = vs[2]; have_v = true; }
+        uint32_t vj[3] = {v[0], v[1], v[2]};
+        wrote_x = true;
+        if (collide_respond(C, nrm, depth, x, vj)) {
+            wrote_v = true;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = vj[c];
+        }
+    }
+    if (wrote_x) { xs[0] = x[0]; xs[1] = x[1]; xs[2] = x[2]; }
+    if (wrote_v) { vs[0] = v[0]; vs[1] = v[1]; vs[2] = v[2]; }
+}
+
+}  // namespace sbk

@@ -589,6 +589,18 @@ int sb_group_place(sb_group *g, const sb_placement *p) {
     return g->for_ranks([&](int r) { return guarded([&]() -> int { return place_validated(g->ranks[(size_t)r], P); }); });
 }
 
+int sb_group_collide(sb_group *g, const sb_collider *colliders, int32_t count) {
+    // null and list checks before the group is touched: refused the same way on a machine without a device
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_collide: null group");
+    if (int rc = validate_colliders("sb_group_collide", colliders, count)) return rc;
+    if (int rc = check_group(g, true, "sb_group_collide")) return rc;
+    if (count == 0) return SB_OK;      // nothing at all: no rank completes its tick
+    // the same list to every rank: each walks what it holds, ghosts included, and completes its tick (a list that touches nothing too: the
+    // ranks stay in the same tick state). The render device takes no part.
+    const std::vector<sb_collider> list(colliders, colliders + count);
+    return g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_validated(g->ranks[(size_t)r], list.data(), count); }); });
+}
+
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */
 
 int sb_group_set_render_triangles(sb_group *g, const int32_t *tri, int32_t m) {

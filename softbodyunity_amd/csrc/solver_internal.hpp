@@ -3,7 +3,7 @@
 //
 // No reference counterpart exists (/root/reference/README.md:1 is the whole reference tree).
 // Units: device_handles.hpp (the owning handle types, the table ring, the first-use rule), binding.hip (errors, RCCL / HIP runtime binding), tables_host.cpp (plan -> host tables, no HIP), stream_codec.hpp (the bit layout of the tile constraint stream: the builder's encoders, the kernels' and the validator's decoders), tables.hip (their upload), launch_shape.hpp (which tile_kernel
-// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), surface_force.hip (wind, air drag and pressure on the render triangles between two ticks), placement.hip (placement between two ticks: one affine map over the whole body), render.hip (render readback: the stage and the entry-point bodies a solver
+// instantiation a launch runs: a pure host function), schedule.hip (launches, ghost exchange, the tick), readback.hip (state reads / writes, where the tick-end positions are, kinematic targets), body_state.hip (mass centre, momenta, best-fit rotation: the reduction and the host derivation), impulse.hip (impulses between two ticks), surface_force.hip (wind, air drag and pressure on the render triangles between two ticks), placement.hip (placement between two ticks: one affine map over the whole body), collide.hip (collider contacts between two ticks: spheres, capsules, boxes against every particle), render.hip (render readback: the stage and the entry-point bodies a solver
 // and a group share -- render.hpp -- and the solver's entry points), authoring.cpp (the authored mesh behind sb_set_* and sb_group_set_*, the
 // window cut; no HIP), validate.hip (table validator), abi.hip (lifecycle, authoring, finalize,
 // stats), plan_abi.hip (host-only planner inspection), group.hip (one process driving several devices).
@@ -397,6 +397,10 @@ void release_surface_tables(sb_solver *s);                                   // 
 // ---- placement.hip: placement between two ticks (SPEC.md 2d) -------------------------------------------------------------------------------
 int validate_placement(const char *who, const sb_placement *p);      // the struct alone: needs neither a group nor a device
 int place_validated(sb_solver *s, const sb_placement &p);            // every local particle, ghosts included; asynchronous on s->stream
+
+// ---- collide.hip: collider contacts between two ticks (SPEC.md 2f) -------------------------------------------------------------------------
+int validate_colliders(const char *who, const sb_collider *colliders, int32_t count);      // the list alone: needs neither a group nor a device
+int collide_validated(sb_solver *s, const sb_collider *colliders, int32_t count);         // count > 0; every local particle, ghosts included; asynchronous on s->stream
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

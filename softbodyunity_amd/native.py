@@ -34,6 +34,7 @@ SB_IMPULSE_VELOCITY_CHANGE, SB_IMPULSE_LINEAR_FALLOFF = 1, 2
 SB_BODY_POSE, SB_BODY_MOTION = 1, 2
 SB_BODY_NO_MASS, SB_BODY_DEGENERATE_POSE, SB_BODY_DEGENERATE_INERTIA = 1, 2, 4
 SB_PLACE_FROM_REFERENCE, SB_PLACE_SET_VELOCITY, SB_PLACE_KEEP_PINNED = 1, 2, 4
+SB_COLLIDER_SPHERE, SB_COLLIDER_CAPSULE, SB_COLLIDER_BOX = 0, 1, 2
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -149,6 +150,14 @@ class SbPlacement(C.Structure):
                 ("lin", C.c_float * 3), ("ang", C.c_float * 3)]
 
 
+class SbCollider(C.Structure):
+    """sb_collider (128 bytes): one entry of sb_group_collide's list (SPEC.md 2f). shape = SB_COLLIDER_*; rot: the box's axes as rows;
+    a is the pivot of ang; flags and reserved stay 0"""
+    _fields_ = [("shape", C.c_uint32), ("flags", C.c_uint32), ("a", C.c_float * 3), ("b", C.c_float * 3), ("rot", C.c_float * 9),
+                ("half", C.c_float * 3), ("radius", C.c_float), ("lin", C.c_float * 3), ("ang", C.c_float * 3), ("friction", C.c_float),
+                ("restitution", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -256,6 +265,7 @@ SIGNATURES = {
     "sb_group_readback_closest_points": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.POINTER(SbClosestHit)]),
     "sb_group_apply_surface_forces": (C.c_int, [_P, C.POINTER(SbSurfaceForce)]),
     "sb_group_place": (C.c_int, [_P, C.POINTER(SbPlacement)]),
+    "sb_group_collide": (C.c_int, [_P, C.POINTER(SbCollider), C.c_int32]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),

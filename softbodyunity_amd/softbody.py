@@ -442,6 +442,42 @@ def make_placement(m=None, frm=(0, 0, 0), to=(0, 0, 0), lin=None, ang=None, from
     return p
 
 
+def _collider(shape, a, lin, ang, friction, restitution):
+    c = native.SbCollider()
+    c.shape = shape
+    c.a[:] = np.asarray(a, np.float32).reshape(3).tolist()
+    c.rot[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    c.lin[:] = np.asarray(lin, np.float32).reshape(3).tolist()
+    c.ang[:] = np.asarray(ang, np.float32).reshape(3).tolist()
+    c.friction, c.restitution = friction, restitution
+    return c
+
+
+def sphere_collider(centre, radius, lin=(0, 0, 0), ang=(0, 0, 0), friction=0.0, restitution=0.0):
+    """-> native.SbCollider (SPEC.md 2f): a sphere about `centre` moving with `lin` and spinning with `ang` (radians per second) about it"""
+    c = _collider(native.SB_COLLIDER_SPHERE, centre, lin, ang, friction, restitution)
+    c.radius = radius
+    return c
+
+
+def capsule_collider(a, b, radius, lin=(0, 0, 0), ang=(0, 0, 0), friction=0.0, restitution=0.0):
+    """-> native.SbCollider (SPEC.md 2f): every point within `radius` of the segment a b; `lin` is the velocity at a, `ang` turns about a"""
+    c = _collider(native.SB_COLLIDER_CAPSULE, a, lin, ang, friction, restitution)
+    c.b[:] = np.asarray(b, np.float32).reshape(3).tolist()
+    c.radius = radius
+    return c
+
+
+def box_collider(centre, half, rot=None, lin=(0, 0, 0), ang=(0, 0, 0), friction=0.0, restitution=0.0):
+    """-> native.SbCollider (SPEC.md 2f): a box about `centre` with half extents `half` along the ROWS of `rot` ((3, 3), orthonormal, not
+    checked; None = the world axes). The rotation matrix R of a transform has the axes as columns: pass R.T."""
+    c = _collider(native.SB_COLLIDER_BOX, centre, lin, ang, friction, restitution)
+    c.half[:] = np.asarray(half, np.float32).reshape(3).tolist()
+    if rot is not None:
+        c.rot[:] = np.asarray(rot, np.float32).reshape(9).tolist()
+    return c
+
+
 def _uv_args(uv):
     """-> (uv (count,2) float32 or None, count) as sb_set_render_uvs takes them"""
     if uv is None:
@@ -595,6 +631,15 @@ class SoftbodyGroup:
         matrix (placement_from_rotation builds one from a quaternion); None = identity. A prepared native.SbPlacement may be given as m."""
         p = m if isinstance(m, native.SbPlacement) else make_placement(m, frm, to, lin, ang, from_reference, keep_pinned)
         check(native.lib().sb_group_place(self._g, C.byref(p)))
+
+    def collide(self, colliders):
+        """Resolve contacts of every particle with a list of moving spheres, capsules and boxes between two ticks, on the devices
+        (sb_group_collide, SPEC.md 2f): a penetrating particle is pushed to the surface and, when it approaches, takes the collider's
+        velocity there with restitution along the normal and Coulomb friction across it. In list order; pinned particles and particles
+        nothing touches keep every bit. colliders: native.SbCollider entries (sphere_collider, capsule_collider, box_collider); an empty
+        list does nothing at all."""
+        items = (native.SbCollider * max(1, len(colliders)))(*colliders)
+        check(native.lib().sb_group_collide(self._g, items, len(colliders)))
 
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
