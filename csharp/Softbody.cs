@@ -5,6 +5,7 @@
 //                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
 //                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
 //                  colliders: sb_group_collide before the step -- the scene's SphereCollider / CapsuleCollider / BoxCollider list in world space, moving with their Rigidbody or transform (SPEC.md 2f)
+//                  collidersFeelBody: sb_group_collide_reactions in its place, and before the next step sb_group_get_collider_reactions -> AddForce / AddTorque on the colliders' rigid bodies (SPEC.md 2g)
 // Teleport() / Respawn() -> sb_group_place: the body follows a requested position and rotation, or starts over from its rest pose (SPEC.md 2d)
 // OnDestroy()   -> sb_group_destroy
 //
@@ -50,8 +51,10 @@ namespace SoftbodyMI355X
         [Tooltip("Pressure along the winding's outward normal, per unit area: inflates a closed skin (negative deflates).")]
         public float internalPressure = 0f;
         [Header("Scene colliders (SPEC.md 2f: contacts resolved before every tick; an empty list = off)")]
-        [Tooltip("SphereCollider, CapsuleCollider and BoxCollider components the body rests on, slides off and is shoved by, in this order. Other collider types and null entries are skipped. Particles collide, not triangles: a collider thinner than the particle spacing passes between them. Nothing acts back on the collider.")]
+        [Tooltip("SphereCollider, CapsuleCollider and BoxCollider components the body rests on, slides off and is shoved by, in this order. Other collider types and null entries are skipped. Particles collide, not triangles: a collider thinner than the particle spacing passes between them. Nothing acts back on the collider unless collidersFeelBody is on.")]
         public Collider[] colliders = new Collider[0];
+        [Tooltip("SPEC.md 2g: every collider of the list with a non-kinematic Rigidbody receives the impulse and the torque the body's contacts gave it, one tick late (GPU solver only). Off: the colliders move as if the body were not there.")]
+        public bool collidersFeelBody = false;
         [Tooltip("Coulomb friction of the body against every collider (>= 0).")]
         public float friction = 0.5f;
         [Tooltip("Restitution of the body against every collider (0 .. 1).")]
@@ -244,6 +247,7 @@ namespace SoftbodyMI355X
         {
             SendImpulses();      // everything queued since the last tick, in one call, before the step
             ApplySurfaceForces();      // wind, air drag, pressure: on the velocities the impulses left, before the step
+            ApplyColliderReactions();  // what the contacts of the tick before gave back to the colliders' rigid bodies (collidersFeelBody)
             SendColliders();           // contacts with the scene's colliders: on the state all of that left, before the step
             bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
@@ -548,6 +552,11 @@ namespace SoftbodyMI355X
         Vector3[] colliderLastPosition = new Vector3[0];
         Quaternion[] colliderLastRotation = new Quaternion[0];
         Collider[] colliderLastSeen = new Collider[0];
+        // reactions (SPEC.md 2g): which collider each record of the last reactions call stood for, and its point a relative to the rigid body's centre of mass (world space)
+        Collider[] colliderOfRecord = new Collider[0];
+        Vector3[] colliderPivotOfRecord = new Vector3[0];
+        SbColliderReaction[] colliderReactions = new SbColliderReaction[0];
+        int reactionsPending = 0;
 
         /// <summary>The inspector list `colliders`, converted to simulation space -- the collider's transform with its scale, then the body's frame --
         /// and sent in ONE sb_group_collide call before the step (SPEC.md 2f): nothing is sent while the list is empty, so a body that touches
@@ -562,6 +571,8 @@ namespace SoftbodyMI355X
             if (colliderRecords.Length != m)
             {
                 colliderRecords = new SbCollider[m]; colliderLastPosition = new Vector3[m]; colliderLastRotation = new Quaternion[m]; colliderLastSeen = new Collider[m];
+                colliderOfRecord = new Collider[m]; colliderPivotOfRecord = new Vector3[m]; colliderReactions = new SbColliderReaction[m];
+                reactionsPending = 0;       // (records of another list length: nothing to hand out)
             }
             float dt = Time.fixedDeltaTime;
             Quaternion toSim = Quaternion.Inverse(FrameRotation());
@@ -620,12 +631,48 @@ namespace SoftbodyMI355X
                 Vector3 aSim = WorldToSimPoint(a), linSim = WorldToSimVector(lin), angSim = toSim * ang;
                 r.aX = aSim.x; r.aY = aSim.y; r.aZ = aSim.z;
                 r.linX = linSim.x; r.linY = linSim.y; r.linZ = linSim.z; r.angX = angSim.x; r.angY = angSim.y; r.angZ = angSim.z;
+                colliderOfRecord[count] = c; colliderPivotOfRecord[count] = rb != null ? a - rb.worldCenterOfMass : Vector3.zero;      // the lever arm a - c as the contact saw it
                 colliderRecords[count++] = r;
             }
             if (count == 0) return;
             bodyHas = 0;
-            if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide(handle, colliderRecords, count), "sb_group_collide");
+            if (handle != IntPtr.Zero && collidersFeelBody && count <= SoftbodyNative.SB_COLLIDE_REACTIONS_MAX)
+            {
+                // the same contacts, bit for bit, and the sums ApplyColliderReactions fetches before the next step
+                SoftbodyNative.Check(SoftbodyNative.sb_group_collide_reactions(handle, colliderRecords, count), "sb_group_collide_reactions");
+                reactionsPending = count;
+            }
+            else if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide(handle, colliderRecords, count), "sb_group_collide");
             else for (int k = 0; k < count; ++k) CollideCpu(colliderRecords[k]);
+        }
+
+        /// <summary>SPEC.md 2g: the impulse J and the angular impulse T_a about the collider's point a that the contacts of the LAST reactions call gave
+        /// each collider, fetched now -- a tick later: the call's kernels ran beside everything since -- and handed to the collider's non-kinematic
+        /// Rigidbody. Back from simulation space by the inverse of what SendColliders applied: J as a vector (a velocity times a mass), T_a as the
+        /// cross product of two such vectors (the frame's rotation, the uniform scale twice). About the body's centre of mass c the torque is
+        /// T_a + (a - c) x J. The coupling is explicit: a rigid body much lighter than contactMass should have its impulse clamped by the host
+        /// (INTEGRATION.md).</summary>
+        void ApplyColliderReactions()
+        {
+            int sent = reactionsPending;
+            reactionsPending = 0;
+            if (sent == 0 || handle == IntPtr.Zero) return;
+            SoftbodyNative.Check(SoftbodyNative.sb_group_get_collider_reactions(handle, colliderReactions, Mathf.Min(sent, colliderReactions.Length), out int count), "sb_group_get_collider_reactions");
+            float worldPerSim = SimToWorldVector(Vector3.right).magnitude;
+            Quaternion toWorld = FrameRotation();
+            for (int k = 0; k < count && k < sent && k < colliderReactions.Length; ++k)
+            {
+                Collider c = colliderOfRecord[k];
+                SbColliderReaction q = colliderReactions[k];
+                if (c == null || q.contacts == 0) continue;
+                Rigidbody rb = c.attachedRigidbody;
+                if (rb == null || rb.isKinematic) continue;
+                Vector3 J = SimToWorldVector(new Vector3((float)q.impulseX, (float)q.impulseY, (float)q.impulseZ));
+                Vector3 Ta = toWorld * new Vector3((float)q.angularImpulseX, (float)q.angularImpulseY, (float)q.angularImpulseZ) * (worldPerSim * worldPerSim);
+                if (!IsFinite(J) || !IsFinite(Ta)) continue;
+                rb.AddForce(J, ForceMode.Impulse);
+                rb.AddTorque(Ta + Vector3.Cross(colliderPivotOfRecord[k], J), ForceMode.Impulse);
+            }
         }
 
         static bool RoundRule(Vector3 x, Vector3 c, float radius, out Vector3 n, out float depth)

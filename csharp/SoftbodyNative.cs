@@ -213,6 +213,17 @@ namespace SoftbodyMI355X
         public int reserved0, reserved1, reserved2;
     }
 
+    /// <summary>sb_collider_reaction (64 bytes): what the body gave back to one collider of sb_group_collide_reactions' list (SPEC.md 2g), in simulation
+    /// space: the impulse, the angular impulse about the collider's point a, the mass and the number of the particles it hit.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbColliderReaction
+    {
+        public double impulseX, impulseY, impulseZ;
+        public double angularImpulseX, angularImpulseY, angularImpulseZ;
+        public double contactMass;
+        public long contacts;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -354,6 +365,9 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_readback_closest_points(IntPtr g, float[] queries, int count, [Out] SbClosestHit[] hits);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_place(IntPtr g, ref SbPlacement placement);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide(IntPtr g, SbCollider[] colliders, int count);
+        public const int SB_COLLIDE_REACTIONS_MAX = 1024;
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide_reactions(IntPtr g, SbCollider[] colliders, int count);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_collider_reactions(IntPtr g, [Out] SbColliderReaction[] reactions, int capacity, out int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);

@@ -260,7 +260,8 @@ int sb_group_place(sb_group *g, const sb_placement *p);
  * A particle with inverse mass 0 is left entirely alone, and a particle that no collider touches keeps every bit of its position and
  * velocity: a call that touches nothing changes nothing. A NaN or infinite position is never hit. A written component that comes out NaN
  * is stored as 0x7fc00000. Contacts are resolved once per call (per tick, not per substep); particles collide, not triangles (a collider
- * thinner than the particle spacing passes between them); nothing acts back on the collider; there is no self-collision. Asynchronous;
+ * thinner than the particle spacing passes between them); this call reports nothing back to the collider (sb_group_collide_reactions below
+ * does); there is no self-collision. Asynchronous;
  * completes every rank's held-back last kernel first, as sb_group_place does, which lands pending kinematic targets; the next tick starts
  * unfused. The ground plane, the render snapshot delivered last, the render device and a render embedding take no part. */
 #define SB_COLLIDER_SPHERE  0u
@@ -281,6 +282,38 @@ typedef struct {
  * before the group is touched), SB_ERR_STATE before sb_group_finalize; a refused call changes nothing. The list is copied before the call
  * returns. No device memory is allocated. Both host models, any number of ranks. */
 int sb_group_collide(sb_group *g, const sb_collider *colliders, int32_t count);
+
+/* ---- reactions: the impulse and torque the body gives back to each collider (SPEC.md 2g) ------------------------------------------------ */
+/* sb_group_collide leaves the colliders alone; this pair reports what Newton's third law owes them, so that the host can apply it to its
+ * rigid bodies (the plugin never moves a collider). sb_group_collide_reactions does to positions and velocities EXACTLY what
+ * sb_group_collide does with the same list -- the same bits, the same ordering rules (completes the held-back kernel, the next tick starts
+ * unfused, count == 0 does nothing to the state, asynchronous), the same refusals and count > SB_COLLIDE_REACTIONS_MAX on top -- and in the
+ * same pass adds up, per collider k of the list, over the particles a rank OWNS (a ghost is its owner's to count) that collider k hit
+ * (inverse mass w > 0, position written), with the state as collider k found it and left it, in binary64 on the binary32 values:
+ *     m = 1 / w,   dv = v_before - v_after (v_after = v_before's bits where the velocity was not written: a separating particle adds
+ *     exactly 0, a non-finite velocity propagates by IEEE rules),   p = x' - a (the binary32 difference of 2f)
+ *     impulse = sum m dv      angular_impulse = sum p x (m dv)      contact_mass = sum m      n_contacts = how many
+ * The position push carries no impulse: only the velocity change is reported. Contraction and the order of additions are free, so the
+ * sums come with an error bound instead of bits (SPEC.md 2g derives it): |sum - exact| <= (n_contacts + 16) 2^-52 A, A the sum of the
+ * absolute values of the elementary products. The same state and list give the same bits (fixed merge order, no atomics); a sum that is
+ * not finite is NaN, +inf or -inf as the exact evaluation is. The first call allocates the workgroups' rows (about 1 byte per particle a
+ * rank holds, counted in sb_stats.device_bytes) and a pinned result of SB_COLLIDE_REACTIONS_MAX records per rank; later calls allocate
+ * nothing, and sb_group_collide never does. */
+typedef struct {
+    double  impulse[3];            /* on the collider, simulation space:  sum m (v_before - v_after) */
+    double  angular_impulse[3];    /* about the collider's point a:       sum p x m (v_before - v_after) */
+    double  contact_mass;          /* sum m over the particles this collider hit */
+    int64_t n_contacts;            /* how many it hit */
+} sb_collider_reaction;            /* 64 bytes */
+#define SB_COLLIDE_REACTIONS_MAX 1024
+int sb_group_collide_reactions(sb_group *g, const sb_collider *colliders, int32_t count);
+/* The records of the LAST sb_group_collide_reactions call, the ranks' rows added in rank order: writes min(count, capacity) records and
+ * the list's count (0 before any such call and after one with count == 0). Waits for that call alone -- an event recorded behind its
+ * launches, no device-wide synchronise: a tick launched after it keeps running and keeps its fused boundary. May be called any number
+ * of times and returns the same bits each time; sb_group_collide, a tick or any other call leaves the stored records alone, the next
+ * reactions call replaces them. SB_ERR_INVALID_ARG (null g or count_out, capacity < 0, null out with capacity > 0), SB_ERR_STATE before
+ * sb_group_finalize. */
+int sb_group_get_collider_reactions(sb_group *g, sb_collider_reaction *out, int32_t capacity, int32_t *count_out);
 
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);

@@ -105,6 +105,7 @@ struct sb_group {
     };
     std::vector<RankRender> rr;
     int64_t dev_bytes = 0;
+    int32_t reaction_count = 0;                  // the list length of the last sb_group_collide_reactions call (SPEC.md 2g): what a fetch returns
 
     int device_of(int r) const { return devices[(size_t)r]; }
     // f(r) for every rank: on the ranks' threads, or one after the other on the calling thread
@@ -599,6 +600,47 @@ int sb_group_collide(sb_group *g, const sb_collider *colliders, int32_t count) {
     // ranks stay in the same tick state). The render device takes no part.
     const std::vector<sb_collider> list(colliders, colliders + count);
     return g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_validated(g->ranks[(size_t)r], list.data(), count); }); });
+}
+
+int sb_group_collide_reactions(sb_group *g, const sb_collider *colliders, int32_t count) {
+    // sb_group_collide's checks in its order, then the one of its own
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_collide_reactions: null group");
+    if (int rc = validate_colliders("sb_group_collide_reactions", colliders, count)) return rc;
+    if (count > SB_COLLIDE_REACTIONS_MAX) return fail(SB_ERR_INVALID_ARG, "sb_group_collide_reactions: more than SB_COLLIDE_REACTIONS_MAX colliders");
+    if (int rc = check_group(g, true, "sb_group_collide_reactions")) return rc;
+    g->reaction_count = 0;             // the stored records are replaced, by nothing if the call fails
+    if (count == 0) return SB_OK;      // nothing at all to the state: no rank completes its tick
+    const std::vector<sb_collider> list(colliders, colliders + count);
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_reactions_validated(g->ranks[(size_t)r], list.data(), count); }); });
+    if (rc) return rc;
+    g->reaction_count = count;
+    return SB_OK;
+}
+
+int sb_group_get_collider_reactions(sb_group *g, sb_collider_reaction *out, int32_t capacity, int32_t *count_out) {
+    if (!g || !count_out) return fail(SB_ERR_INVALID_ARG, "sb_group_get_collider_reactions: null argument");
+    if (capacity < 0) return fail(SB_ERR_INVALID_ARG, "sb_group_get_collider_reactions: negative capacity");
+    if (capacity > 0 && !out) return fail(SB_ERR_INVALID_ARG, "sb_group_get_collider_reactions: null out");
+    if (int rc = check_group(g, true, "sb_group_get_collider_reactions")) return rc;
+    const int32_t count = g->reaction_count, m = std::min(count, capacity);
+    *count_out = count;
+    if (m == 0) return SB_OK;
+    // every rank waits for its own event and hands over its first m records (64 bytes each); the ranks' records are added in rank order,
+    // so the same state and list give the same bits (SPEC.md 2g)
+    std::vector<std::vector<sb_collider_reaction>> part((size_t)g->W, std::vector<sb_collider_reaction>((size_t)m));
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return get_collider_reactions_owned(g->ranks[(size_t)r], part[(size_t)r].data(), m); }); });
+    if (rc) return rc;
+    for (int32_t k = 0; k < m; ++k) {
+        sb_collider_reaction t = part[0][(size_t)k];
+        for (int r = 1; r < g->W; ++r) {
+            const sb_collider_reaction &q = part[(size_t)r][(size_t)k];
+            for (int c = 0; c < 3; ++c) { t.impulse[c] += q.impulse[c]; t.angular_impulse[c] += q.angular_impulse[c]; }
+            t.contact_mass += q.contact_mass;
+            t.n_contacts += q.n_contacts;
+        }
+        out[k] = t;
+    }
+    return SB_OK;
 }
 
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */

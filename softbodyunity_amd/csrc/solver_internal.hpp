@@ -314,6 +314,13 @@ struct sb_solver {
     // ghosts' part is kept on the host by sb_finalize beside ref_pose (12 bytes per ghost); the first such call puts both on the device
     DevBuf<float> d_place_ref;             // packed xyz per local particle, device order
     std::vector<float> ref_pose_ghost;
+    // Reactions (sb_group_collide_reactions, collide.hip; SPEC.md 2g), nothing before the first such call: the workgroups' rows of the pass
+    // and their masks, the rows and masks of the first final level, the mapped pinned records the last level writes
+    // (SB_COLLIDE_REACTIONS_MAX of 8 words each) and the event recorded behind the last batch, which is all a fetch waits for
+    DevBuf<double> d_react_rows, d_react_rows1;
+    DevBuf<uint32_t> d_react_masks, d_react_masks1;
+    sbi::Event ev_react;
+    sbi::HostBuf<double> h_react;
 
     // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
     // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
@@ -401,6 +408,9 @@ int place_validated(sb_solver *s, const sb_placement &p);            // every lo
 // ---- collide.hip: collider contacts between two ticks (SPEC.md 2f) -------------------------------------------------------------------------
 int validate_colliders(const char *who, const sb_collider *colliders, int32_t count);      // the list alone: needs neither a group nor a device
 int collide_validated(sb_solver *s, const sb_collider *colliders, int32_t count);         // count > 0; every local particle, ghosts included; asynchronous on s->stream
+// SPEC.md 2g: the same state, and what the owned particles give back to each collider; 0 < count <= SB_COLLIDE_REACTIONS_MAX; asynchronous
+int collide_reactions_validated(sb_solver *s, const sb_collider *colliders, int32_t count);
+int get_collider_reactions_owned(sb_solver *s, sb_collider_reaction *out, int32_t count);   // waits for the last call above alone; this rank's `count` records
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

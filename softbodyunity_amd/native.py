@@ -158,6 +158,15 @@ class SbCollider(C.Structure):
                 ("restitution", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+class SbColliderReaction(C.Structure):
+    """sb_collider_reaction (64 bytes): what the body gave back to one collider of sb_group_collide_reactions' list (SPEC.md 2g), in
+    simulation space; angular_impulse is about the collider's point a"""
+    _fields_ = [("impulse", C.c_double * 3), ("angular_impulse", C.c_double * 3), ("contact_mass", C.c_double), ("n_contacts", C.c_int64)]
+
+
+SB_COLLIDE_REACTIONS_MAX = 1024
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -266,6 +275,8 @@ SIGNATURES = {
     "sb_group_apply_surface_forces": (C.c_int, [_P, C.POINTER(SbSurfaceForce)]),
     "sb_group_place": (C.c_int, [_P, C.POINTER(SbPlacement)]),
     "sb_group_collide": (C.c_int, [_P, C.POINTER(SbCollider), C.c_int32]),
+    "sb_group_collide_reactions": (C.c_int, [_P, C.POINTER(SbCollider), C.c_int32]),
+    "sb_group_get_collider_reactions": (C.c_int, [_P, C.POINTER(SbColliderReaction), C.c_int32, C.POINTER(C.c_int32)]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),

@@ -641,6 +641,24 @@ class SoftbodyGroup:
         items = (native.SbCollider * max(1, len(colliders)))(*colliders)
         check(native.lib().sb_group_collide(self._g, items, len(colliders)))
 
+    def collide_with_reactions(self, colliders):
+        """collide(colliders), bit for bit, which also adds up on the devices what the body gives back to each collider
+        (sb_group_collide_reactions, SPEC.md 2g); collider_reactions() fetches it. At most native.SB_COLLIDE_REACTIONS_MAX colliders."""
+        items = (native.SbCollider * max(1, len(colliders)))(*colliders)
+        check(native.lib().sb_group_collide_reactions(self._g, items, len(colliders)))
+
+    REACTION_DTYPE = np.dtype([("impulse", np.float64, 3), ("angular_impulse", np.float64, 3), ("contact_mass", np.float64), ("n_contacts", np.int64)])
+
+    def collider_reactions(self, capacity=native.SB_COLLIDE_REACTIONS_MAX):
+        """The reactions of the last collide_with_reactions call (sb_group_get_collider_reactions): a structured array (REACTION_DTYPE), one
+        record per collider in list order -- impulse and angular_impulse (about the collider's point a) in simulation space, the mass
+        and the number of the particles it hit. Waits for that call alone; may be called again and returns the same bits. `capacity`
+        cuts the answer short."""
+        out = np.zeros(max(1, capacity), self.REACTION_DTYPE)
+        count = C.c_int32(0)
+        check(native.lib().sb_group_get_collider_reactions(self._g, out.ctypes.data_as(C.POINTER(native.SbColliderReaction)), capacity, C.byref(count)))
+        return out[:min(count.value, capacity)]
+
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
         check(native.lib().sb_group_set_render_triangles(self._g, tri.ctypes.data_as(C.POINTER(C.c_int32)), tri.shape[0]))
