@@ -5,6 +5,7 @@
 //                  asyncReadback: sb_group_readback_begin/end + GPU vertex normals (and, with UVs, tangents) and the bounding box instead (one tick of latency, no stall)
 //                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
 //                  colliders: sb_group_collide before the step -- the scene's SphereCollider / CapsuleCollider / BoxCollider list in world space, moving with their Rigidbody or transform (SPEC.md 2f)
+//                  terrain: sb_group_set_heightfield when the Terrain or the frame changes, sb_group_collide_heightfield before the step, after the colliders (SPEC.md 2h)
 //                  collidersFeelBody: sb_group_collide_reactions in its place, and before the next step sb_group_get_collider_reactions -> AddForce / AddTorque on the colliders' rigid bodies (SPEC.md 2g)
 // Teleport() / Respawn() -> sb_group_place: the body follows a requested position and rotation, or starts over from its rest pose (SPEC.md 2d)
 // OnDestroy()   -> sb_group_destroy
@@ -59,6 +60,15 @@ namespace SoftbodyMI355X
         public float friction = 0.5f;
         [Tooltip("Restitution of the body against every collider (0 .. 1).")]
         public float bounciness = 0f;
+        [Header("Terrain (SPEC.md 2h: contacts with a height map resolved before every tick; none = off)")]
+        [Tooltip("The Terrain the body lies on. Its height map is read once (TerrainData.GetHeights) and again when the terrain, its data or the body's frame change; call InvalidateTerrain() after painting heights at run time. The terrain is expected upright (Unity terrains do not rotate). Particles collide, not triangles.")]
+        public Terrain terrain = null;
+        [Tooltip("Coulomb friction of the body against the terrain (>= 0).")]
+        public float terrainFriction = 0.5f;
+        [Tooltip("Restitution of the body against the terrain (0 .. 1).")]
+        public float terrainBounciness = 0f;
+        [Tooltip("How far under the terrain's surface, in world units along the surface normal, a particle is still pushed out. Choose it above the fastest expected fall per tick (speed * fixedDeltaTime) and below the depth at which something is meant to be under the ground.")]
+        public float terrainThickness = 1f;
         [Header("Device")]
         [SerializeField] bool useGpu = true;
         [Tooltip("First HIP device ordinal; with deviceCount > 1 the body is split spatially over devices device .. device + deviceCount - 1.")]
@@ -249,6 +259,7 @@ namespace SoftbodyMI355X
             ApplySurfaceForces();      // wind, air drag, pressure: on the velocities the impulses left, before the step
             ApplyColliderReactions();  // what the contacts of the tick before gave back to the colliders' rigid bodies (collidersFeelBody)
             SendColliders();           // contacts with the scene's colliders: on the state all of that left, before the step
+            SendTerrain();             // contacts with the terrain's height map (SPEC.md 2h): after the colliders, before the step
             bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
             {
@@ -644,6 +655,97 @@ namespace SoftbodyMI355X
             }
             else if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide(handle, colliderRecords, count), "sb_group_collide");
             else for (int k = 0; k < count; ++k) CollideCpu(colliderRecords[k]);
+        }
+
+        // ---- terrain (SPEC.md 2h) ----
+        SbHeightfield terrainDesc;
+        float[] terrainHeights;                  // h[iz * nx + ix], simulation units along row 1 of terrainDesc's rot
+        Terrain terrainSent; TerrainData terrainDataSent; Vector3 terrainPositionSent; Matrix4x4 terrainFrameSent; float terrainThicknessSent;
+        bool terrainValid;
+
+        /// <summary>Forget the height map that was read: the next FixedUpdate reads TerrainData.GetHeights again (after heights were painted at run time).</summary>
+        public void InvalidateTerrain() { terrainValid = false; }
+
+        /// <summary>The inspector's `terrain` as SPEC.md 2h's heightfield in simulation space, set once (sb_group_set_heightfield copies it to the
+        /// devices) and again when the terrain, its data, its position or the body's frame change -- the frame moves with the transform unless
+        /// transformFollowsBody froze it at Start --, then ONE sb_group_collide_heightfield call before every step. Unity's height map is
+        /// [z, x] of values in 0 .. 1, scaled by TerrainData.size.y; sample (0, 0) stands at the terrain's position; x grows along world x,
+        /// z along world z. In simulation space these axes are turned by the frame and all lengths scaled by its uniform scale. Nothing is
+        /// sent while `terrain` is null, so a body without one keeps its fused ticks. CPU branch: the same section on the arrays the C#
+        /// solver steps.</summary>
+        void SendTerrain()
+        {
+            if (terrain == null || terrain.terrainData == null)
+            {
+                if (terrainSent != null && handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.ClearHeightfield(handle, IntPtr.Zero, IntPtr.Zero), "sb_group_set_heightfield");
+                terrainSent = null; terrainValid = false;
+                return;
+            }
+            TerrainData data = terrain.terrainData;
+            Matrix4x4 frame = transformFollowsBody ? worldToSim : transform.worldToLocalMatrix;
+            Vector3 origin = terrain.transform.position;
+            if (!terrainValid || terrainSent != terrain || terrainDataSent != data || terrainPositionSent != origin || terrainFrameSent != frame || terrainThicknessSent != terrainThickness)
+            {
+                int res = data.heightmapResolution;                     // samples along x and along z
+                float[,] h01 = data.GetHeights(0, 0, res, res);         // [z, x], 0 .. 1
+                float simPerWorld = WorldToSimVector(Vector3.right).magnitude;      // (the body's transform is expected to be scaled uniformly)
+                Quaternion toSim = Quaternion.Inverse(FrameRotation());
+                Vector3 ax = toSim * Vector3.right, ay = toSim * Vector3.up, az = toSim * Vector3.forward, a = WorldToSimPoint(origin);
+                float up = data.size.y * simPerWorld;
+                if (terrainHeights == null || terrainHeights.Length != res * res) terrainHeights = new float[res * res];
+                for (int iz = 0; iz < res; ++iz)
+                    for (int ix = 0; ix < res; ++ix) terrainHeights[iz * res + ix] = h01[iz, ix] * up;
+                terrainDesc = new SbHeightfield { aX = a.x, aY = a.y, aZ = a.z,
+                                                  rot00 = ax.x, rot01 = ax.y, rot02 = ax.z, rot10 = ay.x, rot11 = ay.y, rot12 = ay.z, rot20 = az.x, rot21 = az.y, rot22 = az.z,
+                                                  cellX = data.size.x / (res - 1) * simPerWorld, cellZ = data.size.z / (res - 1) * simPerWorld, nx = res, nz = res,
+                                                  thickness = Mathf.Max(1e-6f, terrainThickness) * simPerWorld };
+                if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_set_heightfield(handle, ref terrainDesc, terrainHeights), "sb_group_set_heightfield");
+                terrainSent = terrain; terrainDataSent = data; terrainPositionSent = origin; terrainFrameSent = frame; terrainThicknessSent = terrainThickness;
+                terrainValid = true;
+            }
+            bodyHas = 0;
+            float mu = Mathf.Max(0f, terrainFriction), e = Mathf.Clamp01(terrainBounciness);
+            if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide_heightfield(handle, mu, e), "sb_group_collide_heightfield");
+            else CollideHeightfieldCpu(terrainDesc, terrainHeights, mu, e);
+        }
+
+        /// <summary>SPEC.md 2h on the CPU branch's arrays (the order of operations follows the section; C# gives no guarantee against a fused
+        /// multiply-add, so this branch is not bit for bit the plugin).</summary>
+        void CollideHeightfieldCpu(SbHeightfield d, float[] h, float mu, float restitution)
+        {
+            Vector3 a = new Vector3(d.aX, d.aY, d.aZ);
+            Vector3 r0 = new Vector3(d.rot00, d.rot01, d.rot02), r1 = new Vector3(d.rot10, d.rot11, d.rot12), r2 = new Vector3(d.rot20, d.rot21, d.rot22);
+            float mx = d.nx - 1, mz = d.nz - 1;
+            for (int i = 0; i < positions.Length; ++i)
+            {
+                if (!(inverseMass[i] > 0f)) continue;
+                Vector3 x = positions[i], e = x - a;
+                float q0 = Vector3.Dot(e, r0), q1 = Vector3.Dot(e, r1), q2 = Vector3.Dot(e, r2);
+                float fx = q0 / d.cellX, fz = q2 / d.cellZ;
+                if (!(fx >= 0f && fx <= mx && fz >= 0f && fz <= mz)) continue;
+                int ix = Mathf.Min((int)fx, d.nx - 2), iz = Mathf.Min((int)fz, d.nz - 2);
+                float tx = fx - ix, tz = fz - iz;
+                float h00 = h[iz * d.nx + ix], h10 = h[iz * d.nx + ix + 1], h01 = h[(iz + 1) * d.nx + ix], h11 = h[(iz + 1) * d.nx + ix + 1];
+                float sx, sz, height;
+                if (tx + tz <= 1f) { sx = h10 - h00; sz = h01 - h00; height = (h00 + tx * sx) + tz * sz; }
+                else { sx = h11 - h01; sz = h11 - h10; height = (h11 - (1f - tx) * sx) - (1f - tz) * sz; }
+                float gap = height - q1;
+                if (!(gap > 0f)) continue;
+                float gx = sx / d.cellX, gz = sz / d.cellZ, len = Mathf.Sqrt((gx * gx + 1f) + gz * gz);
+                float m0 = -gx / len, m1 = 1f / len, m2 = -gz / len, depth = gap * m1;
+                if (!(depth < d.thickness)) continue;
+                Vector3 n = (m0 * r0 + m1 * r1) + m2 * r2;
+                x += depth * n;
+                positions[i] = x;
+                Vector3 u = velocities[i];                                     // the terrain is at rest: vc = 0
+                float un = Vector3.Dot(u, n);
+                if (!(un < 0f)) continue;                                      // separating: the velocity stays
+                float jn = -un;
+                Vector3 ut = u - un * n;
+                float t2 = Vector3.Dot(ut, ut), tl = Mathf.Sqrt(t2), lim = mu * jn;
+                ut = (t2 > 0f && tl > lim) ? (1f - lim / tl) * ut : Vector3.zero;
+                velocities[i] = ut + (restitution * jn) * n;
+            }
         }
 
         /// <summary>SPEC.md 2g: the impulse J and the angular impulse T_a about the collider's point a that the contacts of the LAST reactions call gave

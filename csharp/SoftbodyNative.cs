@@ -224,6 +224,21 @@ namespace SoftbodyMI355X
         public long contacts;
     }
 
+    /// <summary>sb_heightfield (80 bytes): the frame of sb_group_set_heightfield's height map (SPEC.md 2h). a: sample (0, 0) at height 0, simulation
+    /// space; rot: rows = the axis ix grows along, up, the axis iz grows along; cellX / cellZ: the spacing along rows 0 and 2; heights are
+    /// h[iz * nx + ix] along up; thickness > 0: how far under the surface a particle is still pushed out; flags and reserved stay 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbHeightfield
+    {
+        public float aX, aY, aZ;
+        public float rot00, rot01, rot02, rot10, rot11, rot12, rot20, rot21, rot22;
+        public float cellX, cellZ;
+        public int nx, nz;
+        public float thickness;
+        public uint flags;
+        public int reserved0, reserved1;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -368,6 +383,11 @@ namespace SoftbodyMI355X
         public const int SB_COLLIDE_REACTIONS_MAX = 1024;
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide_reactions(IntPtr g, SbCollider[] colliders, int count);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_collider_reactions(IntPtr g, [Out] SbColliderReaction[] reactions, int capacity, out int count);
+        public const int SB_HEIGHTFIELD_MAX_SAMPLES = 4097;
+        // copies descriptor and heights (nx * nz floats); ClearHeightfield is the same entry point with desc == NULL (clear and release)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_heightfield(IntPtr g, ref SbHeightfield desc, float[] heights);
+        [DllImport(Lib, CallingConvention = CC, EntryPoint = "sb_group_set_heightfield")] public static extern int ClearHeightfield(IntPtr g, IntPtr nullDesc, IntPtr nullHeights);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide_heightfield(IntPtr g, float friction, float restitution);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);

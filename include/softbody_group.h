@@ -315,6 +315,48 @@ int sb_group_collide_reactions(sb_group *g, const sb_collider *colliders, int32_
  * sb_group_finalize. */
 int sb_group_get_collider_reactions(sb_group *g, sb_collider_reaction *out, int32_t capacity, int32_t *count_out);
 
+/* ---- heightfield contacts: a terrain between two ticks (SPEC.md 2h) --------------------------------------------------------------------- */
+/* What a scene's Terrain is to a rigid body: ground that is not flat. A height map of nx * nz samples, h[iz * nx + ix] in simulation units
+ * along `up`, stands in a frame of its own -- sample (0, 0) at height 0 is the point a; ix grows along row 0 of rot, `up` is row 1, iz
+ * grows along row 2 (orthonormal, not checked) -- with the spacing cell[0] along row 0 and cell[1] along row 2. Every cell is two
+ * triangles, cut along the diagonal from sample (ix + 1, iz) to (ix, iz + 1). sb_group_set_heightfield COPIES descriptor and heights (the
+ * caller may free both on return) into a table on every rank's device -- 4 nx nz bytes, counted in sb_stats.device_bytes, given back when
+ * the table is cleared (desc == NULL), replaced (a table of the same size reuses the memory) or the group destroyed. It does not complete
+ * a held-back tick: a set between two ticks leaves their fusion alone. A pass of the table before still in flight is waited for (its
+ * own event, never the device) before its memory is written or released, so that pass reads the table it was given.
+ *
+ * sb_group_collide_heightfield is ONE streaming pass per rank over every particle it holds, ghosts included (the same arithmetic on a
+ * ghost gives its owner's bits: no exchange). Per particle with inverse mass > 0, in binary32 without FMA (SPEC.md 2h has the parentheses):
+ *     q = rot (x - a);   fx = q_0 / cell[0], fz = q_2 / cell[1];   over the grid iff 0 <= fx <= nx - 1 and 0 <= fz <= nz - 1
+ *     height = the cell's triangle under (fx, fz), interpolated;   gap = height - q_1;   m = the triangle's unit normal in the frame
+ *     depth = gap m_1;   hit iff gap > 0 and depth < thickness;    n = m in simulation space
+ * and for a hit 2f's response against a collider at rest with the call's friction and restitution: x' = x + depth n, and the velocity is
+ * written only when the particle approaches. A particle further below the surface than `thickness` (along the normal) is left alone, as
+ * are pinned particles, particles beside the grid and particles above it: they keep every bit. A written component that comes out NaN is
+ * stored as 0x7fc00000. The push goes along the normal of the one triangle under the particle (in a concave crease a particle may land
+ * under the neighbouring triangle until the next call); contacts are resolved once per call, not per substep; particles collide, not
+ * triangles; the terrain is static and gets no reactions. Asynchronous; completes every rank's held-back last kernel first, which lands
+ * pending kinematic targets; the next tick starts unfused. With no heightfield set the call returns SB_OK and does nothing at all (the
+ * tick stays held back). It allocates nothing. Both host models, any number of ranks. */
+#define SB_HEIGHTFIELD_MAX_SAMPLES 4097
+typedef struct {
+    float a[3];                    /* sample (0, 0) at height 0, simulation space */
+    float rot[9];                  /* rows: the axis ix grows along, up, the axis iz grows along */
+    float cell[2];                 /* the spacing along rows 0 and 2, > 0 */
+    int32_t nx, nz;                /* samples along rows 0 and 2: 2 .. SB_HEIGHTFIELD_MAX_SAMPLES */
+    float thickness;               /* > 0: how far under the surface, along the normal, a particle is still pushed out */
+    uint32_t flags;                /* 0 */
+    int32_t reserved[2];           /* 0 */
+} sb_heightfield;                  /* 80 bytes */
+/* desc == NULL clears and releases (heights is then not read). SB_ERR_INVALID_ARG (null group; null heights; nx or nz out of range;
+ * flags or a reserved word != 0; a NaN or infinite float of the descriptor; cell <= 0; thickness <= 0; a NaN or infinite height --
+ * sb_last_error names the first such sample's index --: all checked before the group is touched), SB_ERR_STATE before
+ * sb_group_finalize; a refused call changes nothing and keeps the table set before. */
+int sb_group_set_heightfield(sb_group *g, const sb_heightfield *desc, const float *heights);
+/* SB_ERR_INVALID_ARG (null group, friction < 0 or NaN or infinite, restitution outside [0, 1]), SB_ERR_STATE before sb_group_finalize; a
+ * refused call changes nothing. */
+int sb_group_collide_heightfield(sb_group *g, float friction, float restitution);
+
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);
 int32_t sb_group_rank_count(const sb_group *g);

@@ -105,6 +105,7 @@ struct sb_group {
     };
     std::vector<RankRender> rr;
     int64_t dev_bytes = 0;
+    bool heightfield_set = false;                // sb_group_set_heightfield left a table on every rank (SPEC.md 2h)
     int32_t reaction_count = 0;                  // the list length of the last sb_group_collide_reactions call (SPEC.md 2g): what a fetch returns
 
     int device_of(int r) const { return devices[(size_t)r]; }
@@ -641,6 +642,37 @@ int sb_group_get_collider_reactions(sb_group *g, sb_collider_reaction *out, int3
         out[k] = t;
     }
     return SB_OK;
+}
+
+int sb_group_set_heightfield(sb_group *g, const sb_heightfield *desc, const float *heights) {
+    // null and table checks before the group is touched: refused the same way on a machine without a device
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_heightfield: null group");
+    if (desc)
+        if (int rc = validate_heightfield("sb_group_set_heightfield", desc, heights)) return rc;
+    if (int rc = check_group(g, true, "sb_group_set_heightfield")) return rc;
+    // no rank completes its tick: the table has a lifetime of its own, and a held-back last kernel still fuses with the next tick
+    if (!desc) {
+        if (!g->heightfield_set) return SB_OK;
+        g->heightfield_set = false;
+        return g->for_ranks([&](int r) { return guarded([&]() -> int { return clear_heightfield(g->ranks[(size_t)r]); }); });
+    }
+    const sb_heightfield D = *desc;
+    const float top = heightfield_top(heights, (int64_t)D.nx * D.nz);
+    g->heightfield_set = false;        // (set again once every rank has its table: a failure half way leaves no table in force)
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return set_heightfield_validated(g->ranks[(size_t)r], D, heights, top); }); });
+    if (rc) return rc;
+    g->heightfield_set = true;
+    return SB_OK;
+}
+
+int sb_group_collide_heightfield(sb_group *g, float friction, float restitution) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_collide_heightfield: null group");
+    if (int rc = validate_heightfield_call("sb_group_collide_heightfield", friction, restitution)) return rc;
+    if (int rc = check_group(g, true, "sb_group_collide_heightfield")) return rc;
+    if (!g->heightfield_set) return SB_OK;      // nothing at all: no rank completes its tick (sb_group_collide's count == 0)
+    // every rank walks what it holds, ghosts included, and completes its tick (a table that touches nothing too: the ranks stay in the same
+    // tick state). The render device takes no part.
+    return g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_heightfield_validated(g->ranks[(size_t)r], friction, restitution); }); });
 }
 
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */

@@ -321,6 +321,14 @@ struct sb_solver {
     DevBuf<uint32_t> d_react_masks, d_react_masks1;
     sbi::Event ev_react;
     sbi::HostBuf<double> h_react;
+    // Heightfield (sb_group_set_heightfield, heightfield.hip; SPEC.md 2h), nothing before the first set: the rank's copy of the heights, the
+    // descriptor they came with, the cull height made of them, and the event recorded behind the last pass that read the table -- what a
+    // later set or clear waits for before the memory is written or released
+    DevBuf<float> d_hf;
+    sb_heightfield hf_desc{};
+    float hf_top = 0.0f;
+    bool hf_set = false, hf_in_flight = false;
+    sbi::Event ev_hf_read;
 
     // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
     // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
@@ -411,6 +419,14 @@ int collide_validated(sb_solver *s, const sb_collider *colliders, int32_t count)
 // SPEC.md 2g: the same state, and what the owned particles give back to each collider; 0 < count <= SB_COLLIDE_REACTIONS_MAX; asynchronous
 int collide_reactions_validated(sb_solver *s, const sb_collider *colliders, int32_t count);
 int get_collider_reactions_owned(sb_solver *s, sb_collider_reaction *out, int32_t count);   // waits for the last call above alone; this rank's `count` records
+
+// ---- heightfield.hip: contacts with a terrain heightfield between two ticks (SPEC.md 2h) ---------------------------------------------------
+int validate_heightfield(const char *who, const sb_heightfield *d, const float *heights);      // descriptor and heights alone: needs neither a group nor a device
+int validate_heightfield_call(const char *who, float friction, float restitution);
+float heightfield_top(const float *heights, int64_t count);                                     // no rounded height of the table exceeds it
+int set_heightfield_validated(sb_solver *s, const sb_heightfield &d, const float *heights, float top);      // copies; leaves the tick's stream alone
+int clear_heightfield(sb_solver *s);
+int collide_heightfield_validated(sb_solver *s, float friction, float restitution);            // every local particle, ghosts included; asynchronous on s->stream
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

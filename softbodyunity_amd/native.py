@@ -35,6 +35,7 @@ SB_BODY_POSE, SB_BODY_MOTION = 1, 2
 SB_BODY_NO_MASS, SB_BODY_DEGENERATE_POSE, SB_BODY_DEGENERATE_INERTIA = 1, 2, 4
 SB_PLACE_FROM_REFERENCE, SB_PLACE_SET_VELOCITY, SB_PLACE_KEEP_PINNED = 1, 2, 4
 SB_COLLIDER_SPHERE, SB_COLLIDER_CAPSULE, SB_COLLIDER_BOX = 0, 1, 2
+SB_HEIGHTFIELD_MAX_SAMPLES = 4097
 SB_ERR_INVALID_ARG, SB_ERR_STATE, SB_ERR_NO_DEVICE, SB_ERR_HIP, SB_ERR_RCCL, SB_ERR_NOMEM, SB_ERR_UNSUPPORTED = \
     -1, -2, -3, -4, -5, -6, -7
 
@@ -167,6 +168,28 @@ class SbColliderReaction(C.Structure):
 SB_COLLIDE_REACTIONS_MAX = 1024
 
 
+class SbHeightfield(C.Structure):
+    """sb_heightfield (80 bytes): the frame of sb_group_set_heightfield's height map (SPEC.md 2h). a: sample (0, 0) at height 0; rot: rows
+    = the axis ix grows along, up, the axis iz grows along; cell: the spacing along rows 0 and 2; flags and reserved stay 0"""
+    _fields_ = [("a", C.c_float * 3), ("rot", C.c_float * 9), ("cell", C.c_float * 2), ("nx", C.c_int32), ("nz", C.c_int32),
+                ("thickness", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
+def heightfield(a, cell, heights2d, rot=None, thickness=1.0):
+    """-> (SbHeightfield, heights) as sb_group_set_heightfield takes them. heights2d: (nz, nx), heights2d[iz, ix] in simulation units
+    along `up`; cell: one spacing or (along ix, along iz); rot: (3, 3) with the ROWS ix axis, up, iz axis (None = x, y, z)."""
+    h = np.ascontiguousarray(heights2d, dtype=np.float32)
+    if h.ndim != 2:
+        raise ValueError("heights2d must be (nz, nx)")
+    d = SbHeightfield()
+    d.a[:] = np.asarray(a, np.float32).reshape(3).tolist()
+    d.rot[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1] if rot is None else np.asarray(rot, np.float32).reshape(9).tolist()
+    d.cell[:] = np.broadcast_to(np.asarray(cell, np.float32), (2,)).tolist()
+    d.nz, d.nx = h.shape
+    d.thickness = thickness
+    return d, h
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -277,6 +300,8 @@ SIGNATURES = {
     "sb_group_collide": (C.c_int, [_P, C.POINTER(SbCollider), C.c_int32]),
     "sb_group_collide_reactions": (C.c_int, [_P, C.POINTER(SbCollider), C.c_int32]),
     "sb_group_get_collider_reactions": (C.c_int, [_P, C.POINTER(SbColliderReaction), C.c_int32, C.POINTER(C.c_int32)]),
+    "sb_group_set_heightfield": (C.c_int, [_P, C.POINTER(SbHeightfield), C.POINTER(C.c_float)]),
+    "sb_group_collide_heightfield": (C.c_int, [_P, C.c_float, C.c_float]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),

@@ -659,6 +659,26 @@ class SoftbodyGroup:
         check(native.lib().sb_group_get_collider_reactions(self._g, out.ctypes.data_as(C.POINTER(native.SbColliderReaction)), capacity, C.byref(count)))
         return out[:min(count.value, capacity)]
 
+    def set_heightfield(self, desc, heights):
+        """Put a terrain height map on every rank's device (sb_group_set_heightfield, SPEC.md 2h): desc and heights as
+        native.heightfield(a, cell, heights2d, rot, thickness) returns them. Copies; replaces a table set before; does not complete a
+        held-back tick."""
+        h = np.ascontiguousarray(heights, dtype=np.float32)
+        if h.size != desc.nx * desc.nz:
+            raise ValueError("heights must hold nx * nz samples")
+        check(native.lib().sb_group_set_heightfield(self._g, C.byref(desc), h.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def clear_heightfield(self):
+        """Clear the heightfield and release its device memory; collide_heightfield then does nothing."""
+        check(native.lib().sb_group_set_heightfield(self._g, None, None))
+
+    def collide_heightfield(self, friction=0.0, restitution=0.0):
+        """Resolve the contacts of every particle with the heightfield set last, between two ticks, on the devices
+        (sb_group_collide_heightfield, SPEC.md 2h): a particle under the surface, by less than the table's thickness along the normal, is
+        pushed onto the triangle above it and, when it approaches, loses its normal velocity but for `restitution` and its tangential one
+        by Coulomb `friction`. Everything else keeps every bit; with no heightfield set the call does nothing at all."""
+        check(native.lib().sb_group_collide_heightfield(self._g, friction, restitution))
+
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
         check(native.lib().sb_group_set_render_triangles(self._g, tri.ctypes.data_as(C.POINTER(C.c_int32)), tri.shape[0]))
