@@ -186,7 +186,9 @@ int sb_set_state(sb_solver *s, const float *pos_xyz, const float *vel_xyz, int32
  * pull their neighbours along. An id whose inverse mass is not 0 is refused (SB_ERR_INVALID_ARG, nothing is changed). Asynchronous like
  * sb_step (the targets are copied before the call returns). The targets are pending until the next tick starts: when that tick's first
  * kernel also finishes the previous tick (the lazy tick boundary of sb_step) they are applied inside it, so a host that moves its pins
- * every tick keeps the fusion (sb_stats.ticks_fused_kinematic); position reads in between already show them. A rank of a partitioned solver
+ * every tick keeps the fusion (sb_stats.ticks_fused_kinematic); position reads in between already show them. A second call while targets
+ * are still pending (two moves without a tick between them) lets the earlier ones take effect first: it completes the tick's held-back last
+ * kernel, so the next sb_step starts unfused and carries the later move along unfused. A rank of a partitioned solver
  * (world > 1) is given the same list in its own numbering (the whole list on every rank is fine): every entry is validated, the rank applies
  * the particles it OWNS and skips the others -- their owners apply them, and the ghost copies arrive with the next exchange. */
 int sb_set_kinematic_positions(sb_solver *s, const int32_t *ids, const float *pos_xyz, int32_t count);

@@ -82,10 +82,16 @@ int sb_group_finalize(sb_group *g);
 int sb_group_step(sb_group *g, float dt, int32_t substeps);
 
 /* ---- state, gathered in the caller's numbering --------------------------------------------------------------------------------------------- */
+/* What these do to a tick whose last kernel is held back (softbody.h, sb_step), on every rank alike: sb_group_get_positions peeks where
+ * sb_get_positions peeks (the tick stays fusable, pending kinematic targets show and stay pending) and completes the tick elsewhere;
+ * sb_group_get_velocities and sb_group_set_state complete it and land pending kinematic targets: the next sb_group_step starts unfused. */
 int sb_group_get_positions(sb_group *g, float *pos_xyz_out, int32_t n);      /* every entry written: each rank delivers what it owns */
 int sb_group_get_velocities(sb_group *g, float *vel_xyz_out, int32_t n);
 int sb_group_set_state(sb_group *g, const float *pos_xyz, const float *vel_xyz, int32_t n);
-/* Kinematic targets (sb_set_kinematic_positions): ids in the caller's numbering, each at most once; every rank takes the ones it owns. */
+/* Kinematic targets (sb_set_kinematic_positions): ids in the caller's numbering, each at most once; every rank takes the ones it owns.
+ * The call leaves a held-back tick held back, and the move rides the next tick's fused first kernel -- unless targets of an earlier call
+ * are still pending on any rank (two moves without a tick between them): the earlier one takes effect first, which completes the tick on
+ * EVERY rank, also on one that owns none of either call's targets, so that the ranks stay in the same tick state. */
 int sb_group_set_kinematic_positions(sb_group *g, const int32_t *ids, const float *pos_xyz, int32_t count);
 /* Impulses between two ticks (sb_apply_impulses, SPEC.md 2c), same contract, in the whole mesh's numbering: the list is validated once,
  * SURFACE items are expanded on the host from the group's own copies of the triangles and the embedding (a cage may straddle ranks),

@@ -12,6 +12,8 @@ What varies per scenario (all from one seed, printed, so a failure replays with 
   actions   between ticks: set_state, the ground plane moved or switched, kinematic moves of pinned particles, a blocking position read (the
             peek / the flush), a tick with its own dt and substeps, a pipelined render readback (whole array, with GPU normals, render set
             only) -- each mirrored on the oracle
+The between-tick calls that came later (impulses, placement, surface forces, contacts, reactions, queries) are interleaved by
+tests/fuzz/fuzz_frames.py, a generator of its own: this one's seeds keep their meaning.
 Every scenario also runs the table validator. usage: python tests/fuzz/fuzz_parity.py [--seconds 240] [--seed 0] [--only SEED] [--max N]"""
 import argparse
 import ctypes as C
