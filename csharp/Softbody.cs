@@ -6,6 +6,7 @@
 //                  transformFollowsBody: + sb_group_get_body_state(POSE), the transform set to the frame that fits the body best (SPEC.md 6f)
 //                  colliders: sb_group_collide before the step -- the scene's SphereCollider / CapsuleCollider / BoxCollider list in world space, moving with their Rigidbody or transform (SPEC.md 2f)
 //                  terrain: sb_group_set_heightfield when the Terrain or the frame changes, sb_group_collide_heightfield before the step, after the colliders (SPEC.md 2h)
+//                  distanceFieldProps: sb_group_set_distance_field once per baked asset, sb_group_collide_distance_field per prop with its Transform's pose and velocities before the step, after the terrain (SPEC.md 2i)
 //                  collidersFeelBody: sb_group_collide_reactions in its place, and before the next step sb_group_get_collider_reactions -> AddForce / AddTorque on the colliders' rigid bodies (SPEC.md 2g)
 // Teleport() / Respawn() -> sb_group_place: the body follows a requested position and rotation, or starts over from its rest pose (SPEC.md 2d)
 // OnDestroy()   -> sb_group_destroy
@@ -29,6 +30,31 @@ using UnityEngine;
 
 namespace SoftbodyMI355X
 {
+    /// <summary>A prop baked into a signed-distance table (SPEC.md 2i; softbodyunity_amd.signed_distance_grid writes these numbers): nx * ny * nz
+    /// samples, samples[(iz * ny + iy) * nx + ix], distances in the prop's local units, negative inside, `cell` apart, sample (0, 0, 0) at
+    /// the local position `origin`.</summary>
+    [CreateAssetMenu(menuName = "Softbody/Distance field")]
+    public class SoftbodyDistanceFieldAsset : ScriptableObject
+    {
+        public int nx, ny, nz;
+        public Vector3 cell = Vector3.one;
+        public Vector3 origin;
+        public float[] samples;
+    }
+
+    /// <summary>One entry of Softbody.distanceFieldProps: a baked asset and the Transform that carries it.</summary>
+    [Serializable]
+    public class DistanceFieldProp
+    {
+        public SoftbodyDistanceFieldAsset asset;
+        public Transform transform;
+        [Tooltip("Coulomb friction of the body against the prop (>= 0).")] public float friction = 0.5f;
+        [Tooltip("Restitution of the body against the prop (0 .. 1).")] public float bounciness = 0f;
+        [Tooltip("A skin round the baked surface, world units: the contact surface is the level set phi = offset.")] public float offset = 0f;
+        [Tooltip("How deep under the contact surface, world units, a particle is still pushed out: above the fastest closing motion per tick, below half the prop's thinnest wall.")] public float thickness = 0.5f;
+        [NonSerialized] public bool seen; [NonSerialized] public Vector3 lastA; [NonSerialized] public Quaternion lastQ;      // the pose sent last, simulation space
+    }
+
     [RequireComponent(typeof(MeshFilter))]
     public class Softbody : MonoBehaviour
     {
@@ -69,6 +95,10 @@ namespace SoftbodyMI355X
         public float terrainBounciness = 0f;
         [Tooltip("How far under the terrain's surface, in world units along the surface normal, a particle is still pushed out. Choose it above the fastest expected fall per tick (speed * fixedDeltaTime) and below the depth at which something is meant to be under the ground.")]
         public float terrainThickness = 1f;
+
+        [Header("Props of any shape (SPEC.md 2i: contacts with baked signed-distance volumes resolved before every tick; empty = off)")]
+        [Tooltip("Each entry is a baked asset (softbodyunity_amd.signed_distance_grid: dimensions, cell, samples, the local position of sample (0, 0, 0)) and the Transform that carries it. The asset goes to the GPUs once; the Transform's pose and its change since the last tick are sent before every step, after the colliders and the terrain. At most SB_DISTANCE_FIELD_SLOTS (4) different assets; entries that share an asset share its table (instances). GPU branch only.")]
+        public DistanceFieldProp[] distanceFieldProps = new DistanceFieldProp[0];
         [Header("Device")]
         [SerializeField] bool useGpu = true;
         [Tooltip("First HIP device ordinal; with deviceCount > 1 the body is split spatially over devices device .. device + deviceCount - 1.")]
@@ -260,6 +290,7 @@ namespace SoftbodyMI355X
             ApplyColliderReactions();  // what the contacts of the tick before gave back to the colliders' rigid bodies (collidersFeelBody)
             SendColliders();           // contacts with the scene's colliders: on the state all of that left, before the step
             SendTerrain();             // contacts with the terrain's height map (SPEC.md 2h): after the colliders, before the step
+            SendDistanceFieldProps();  // contacts with baked props of any shape (SPEC.md 2i): after the terrain, before the step
             bodyHas = 0;         // (the state is about to change)
             if (useGpu && asyncReadback)
             {
@@ -707,6 +738,80 @@ namespace SoftbodyMI355X
             float mu = Mathf.Max(0f, terrainFriction), e = Mathf.Clamp01(terrainBounciness);
             if (handle != IntPtr.Zero) SoftbodyNative.Check(SoftbodyNative.sb_group_collide_heightfield(handle, mu, e), "sb_group_collide_heightfield");
             else CollideHeightfieldCpu(terrainDesc, terrainHeights, mu, e);
+        }
+
+        // ---- props of any shape (SPEC.md 2i) ----
+        SoftbodyDistanceFieldAsset[] slotAsset = new SoftbodyDistanceFieldAsset[SoftbodyNative.SB_DISTANCE_FIELD_SLOTS];
+        float[] slotScale = new float[SoftbodyNative.SB_DISTANCE_FIELD_SLOTS], slotOffset = new float[SoftbodyNative.SB_DISTANCE_FIELD_SLOTS], slotThickness = new float[SoftbodyNative.SB_DISTANCE_FIELD_SLOTS];
+        bool warnedAboutSlots;
+
+        /// <summary>The inspector's `distanceFieldProps` as SPEC.md 2i's tables and poses. An asset is sent to a slot ONCE
+        /// (sb_group_set_distance_field copies it to the devices; its distances and cells are scaled to simulation units, so it is sent
+        /// again when the prop's or the body's scale, `offset` or `thickness` change); the pose -- where the asset's sample (0, 0, 0) stands
+        /// in simulation space, the prop's axes there, and the velocities read off the pose's change since the last tick -- goes with ONE
+        /// sb_group_collide_distance_field call per entry before every step. Entries with the same asset and skin share a slot. A slot
+        /// nobody uses any more is cleared. Nothing is sent while the list is empty, so a body without props keeps its fused ticks. The
+        /// CPU branch has no counterpart: props are skipped there.</summary>
+        void SendDistanceFieldProps()
+        {
+            if (handle == IntPtr.Zero) return;
+            bool[] used = new bool[SoftbodyNative.SB_DISTANCE_FIELD_SLOTS];
+            float simPerWorld = WorldToSimVector(Vector3.right).magnitude;      // (the body's transform is expected to be scaled uniformly)
+            Quaternion toSim = Quaternion.Inverse(FrameRotation());
+            float dt = Mathf.Max(1e-6f, Time.fixedDeltaTime);
+            foreach (DistanceFieldProp p in distanceFieldProps)
+            {
+                if (p == null || p.asset == null || p.transform == null || p.asset.samples == null) continue;
+                SoftbodyDistanceFieldAsset A = p.asset;
+                float scale = p.transform.lossyScale.x * simPerWorld;           // (props are expected to be scaled uniformly, too)
+                float offset = Mathf.Max(0f, p.offset) * simPerWorld, thickness = Mathf.Max(1e-6f, p.thickness) * simPerWorld;
+                int slot = -1;
+                for (int s = 0; s < slotAsset.Length && slot < 0; ++s)
+                    if (slotAsset[s] == A && slotScale[s] == scale && slotOffset[s] == offset && slotThickness[s] == thickness) slot = s;
+                for (int s = 0; s < slotAsset.Length && slot < 0; ++s)
+                    if (slotAsset[s] == null && !used[s])
+                    {
+                        var desc = new SbDistanceField { nx = A.nx, ny = A.ny, nz = A.nz, cellX = A.cell.x * scale, cellY = A.cell.y * scale, cellZ = A.cell.z * scale,
+                                                         offset = offset, thickness = thickness };
+                        float[] scaled = new float[A.samples.Length];
+                        for (int i = 0; i < scaled.Length; ++i) scaled[i] = A.samples[i] * scale;
+                        SoftbodyNative.Check(SoftbodyNative.sb_group_set_distance_field(handle, s, ref desc, scaled), "sb_group_set_distance_field");
+                        slotAsset[s] = A; slotScale[s] = scale; slotOffset[s] = offset; slotThickness[s] = thickness;
+                        slot = s;
+                    }
+                if (slot < 0)
+                {
+                    if (!warnedAboutSlots) Debug.LogWarning("Softbody: more than " + slotAsset.Length + " different distance-field assets; the rest are ignored");
+                    warnedAboutSlots = true;
+                    continue;
+                }
+                used[slot] = true;
+                // the pose: sample (0, 0, 0) and the prop's axes in simulation space; velocities from the change since the last tick
+                Vector3 a = WorldToSimPoint(p.transform.TransformPoint(A.origin));
+                Quaternion q = toSim * p.transform.rotation;
+                Vector3 ax = q * Vector3.right, ay = q * Vector3.up, az = q * Vector3.forward;
+                Vector3 lin = Vector3.zero, ang = Vector3.zero;
+                if (p.seen)
+                {
+                    lin = (a - p.lastA) / dt;                                   // the velocity of the point a itself: what SPEC.md 2i's lin is
+                    (q * Quaternion.Inverse(p.lastQ)).ToAngleAxis(out float degrees, out Vector3 axis);
+                    if (degrees > 180f) degrees -= 360f;
+                    if (!float.IsNaN(axis.x) && !float.IsInfinity(axis.x)) ang = axis * (degrees * Mathf.Deg2Rad / dt);
+                }
+                p.lastA = a; p.lastQ = q; p.seen = true;
+                var pose = new SbDistanceFieldPose { aX = a.x, aY = a.y, aZ = a.z,
+                                                     rot00 = ax.x, rot01 = ax.y, rot02 = ax.z, rot10 = ay.x, rot11 = ay.y, rot12 = ay.z, rot20 = az.x, rot21 = az.y, rot22 = az.z,
+                                                     linX = lin.x, linY = lin.y, linZ = lin.z, angX = ang.x, angY = ang.y, angZ = ang.z,
+                                                     friction = Mathf.Max(0f, p.friction), restitution = Mathf.Clamp01(p.bounciness) };
+                SoftbodyNative.Check(SoftbodyNative.sb_group_collide_distance_field(handle, slot, ref pose), "sb_group_collide_distance_field");
+                bodyHas = 0;
+            }
+            for (int s = 0; s < slotAsset.Length; ++s)
+                if (slotAsset[s] != null && !used[s])
+                {
+                    SoftbodyNative.Check(SoftbodyNative.ClearDistanceField(handle, s, IntPtr.Zero, IntPtr.Zero), "sb_group_set_distance_field");
+                    slotAsset[s] = null;
+                }
         }
 
         /// <summary>SPEC.md 2h on the CPU branch's arrays (the order of operations follows the section; C# gives no guarantee against a fused

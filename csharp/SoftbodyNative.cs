@@ -239,6 +239,33 @@ namespace SoftbodyMI355X
         public int reserved0, reserved1;
     }
 
+    /// <summary>sb_distance_field (48 bytes): the shape of sb_group_set_distance_field's table (SPEC.md 2i). nx, ny, nz: samples along the
+    /// frame's rows 0, 1, 2, s[(iz * ny + iy) * nx + ix], signed distances in simulation units, negative inside; cellX/Y/Z: the spacing along
+    /// the rows; offset >= 0: the contact surface is phi = offset; thickness > 0: how deep under it a particle is still pushed out; flags and
+    /// reserved stay 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbDistanceField
+    {
+        public int nx, ny, nz;
+        public float cellX, cellY, cellZ;
+        public float offset, thickness;
+        public uint flags;
+        public int reserved0, reserved1, reserved2;
+    }
+
+    /// <summary>sb_distance_field_pose (88 bytes): where a slot's table stands and how it moves, per call (SPEC.md 2i). a: sample (0, 0, 0),
+    /// simulation space, and the pivot of ang; rot: rows = the axes ix, iy, iz grow along; lin / ang: the prop's velocity at a and its angular
+    /// velocity; reserved stays 0.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SbDistanceFieldPose
+    {
+        public float aX, aY, aZ;
+        public float rot00, rot01, rot02, rot10, rot11, rot12, rot20, rot21, rot22;
+        public float linX, linY, linZ, angX, angY, angZ;
+        public float friction, restitution;
+        public int reserved0, reserved1;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct SbPhaseInfo
     {
@@ -388,6 +415,11 @@ namespace SoftbodyMI355X
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_heightfield(IntPtr g, ref SbHeightfield desc, float[] heights);
         [DllImport(Lib, CallingConvention = CC, EntryPoint = "sb_group_set_heightfield")] public static extern int ClearHeightfield(IntPtr g, IntPtr nullDesc, IntPtr nullHeights);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide_heightfield(IntPtr g, float friction, float restitution);
+        public const int SB_DISTANCE_FIELD_SLOTS = 4, SB_DISTANCE_FIELD_MAX_DIM = 1024, SB_DISTANCE_FIELD_MAX_SAMPLES = 1 << 27;
+        // copies descriptor and samples (nx * ny * nz floats) into the slot; ClearDistanceField is the same entry point with desc == NULL (clear and release)
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_set_distance_field(IntPtr g, int slot, ref SbDistanceField desc, float[] samples);
+        [DllImport(Lib, CallingConvention = CC, EntryPoint = "sb_group_set_distance_field")] public static extern int ClearDistanceField(IntPtr g, int slot, IntPtr nullDesc, IntPtr nullSamples);
+        [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_collide_distance_field(IntPtr g, int slot, ref SbDistanceFieldPose pose);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_get_body_state(IntPtr g, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_body_state_from_sums(double[] sums32, long nDynamic, long nPinned, uint what, out SbBodyState state);
         [DllImport(Lib, CallingConvention = CC)] public static extern int sb_group_synchronize(IntPtr g);

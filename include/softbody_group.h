@@ -363,6 +363,60 @@ int sb_group_set_heightfield(sb_group *g, const sb_heightfield *desc, const floa
  * refused call changes nothing. */
 int sb_group_collide_heightfield(sb_group *g, float friction, float restitution);
 
+/* ---- signed-distance volumes: moving props of any shape between two ticks (SPEC.md 2i) ------------------------------------------------------ */
+/* What a scene's MeshCollider is to a rigid body: a bowl, a staircase, a cave with overhangs, a turning gear. The prop is baked once into a
+ * table of nx * ny * nz signed distances (negative inside, simulation units), s[(iz * ny + iy) * nx + ix], on a regular grid with the
+ * spacing cell[k] along axis k. The table holds the SHAPE and goes to a slot (SB_DISTANCE_FIELD_SLOTS of them); where it stands and how
+ * it moves -- the POSE -- comes with every call, so a prop moves and turns every tick with nothing uploaded, and one slot may be used at
+ * several poses in one frame (instances of one prop). sb_group_set_distance_field COPIES descriptor and samples (the caller may free both
+ * on return) into a table on every rank's device -- 4 nx ny nz bytes, counted in sb_stats.device_bytes, given back when the slot is
+ * cleared (desc == NULL), replaced (a table of the same size reuses the memory) or the group destroyed. It does not complete a held-back
+ * tick. A pass of that slot still in flight is waited for (its own event, never the device) before the slot's memory is written or
+ * released, so that pass reads the table it was given.
+ *
+ * sb_group_collide_distance_field is ONE streaming pass per rank over every particle it holds, ghosts included (the same arithmetic on a
+ * ghost gives its owner's bits: no exchange). Per particle with inverse mass > 0, in binary32 without FMA (SPEC.md 2i has the parentheses):
+ *     q = rot (x - a);   f_k = q_k / cell[k];   in the volume iff 0 <= f_k <= n_k - 1 for k = 0, 1, 2
+ *     phi = the trilinear interpolation of the cell's eight samples, G = its analytic gradient in the frame
+ *     gap = offset - phi;   hit iff gap > 0, gap < thickness and |G| > 0;   n = rot^T G / |G|;   depth = gap
+ * and for a hit 2f's response against a collider with the pose's a, lin, ang, friction and restitution: x' = x + depth n, and the velocity
+ * is written only when the particle approaches. Pinned particles, particles outside the volume, particles on or outside the contact
+ * surface phi = offset and particles deeper under it than `thickness` keep every bit; a call that touches nothing is a bit-identity. A
+ * written component that comes out NaN is stored as 0x7fc00000. Asynchronous; completes every rank's held-back last kernel first, which
+ * lands pending kinematic targets; the next tick starts unfused. With nothing set in `slot` the call returns SB_OK and does nothing at all
+ * (the tick stays held back). It allocates nothing. Both host models, any number of ranks. Several props are several calls, applied in
+ * call order.
+ * NOT DONE: contacts are resolved once per call, not per substep; particles collide, not triangles; the prop gets no reactions; there
+ * is no brick-level cull (every particle inside the footprint gathers its eight samples); a trilinear field rounds off features thinner
+ * than a cell. */
+#define SB_DISTANCE_FIELD_SLOTS        4          /* tables a group can hold at once */
+#define SB_DISTANCE_FIELD_MAX_DIM      1024       /* samples along one axis: 2 .. this */
+#define SB_DISTANCE_FIELD_MAX_SAMPLES  (1 << 27)  /* nx*ny*nz: 512 MiB of float; the flat index fits an int32 */
+typedef struct {
+    int32_t nx, ny, nz;        /* samples along the frame's rows 0, 1, 2; s[(iz*ny + iy)*nx + ix] */
+    float   cell[3];           /* spacing along the rows, > 0 */
+    float   offset;            /* >= 0: the contact surface is the level set phi = offset (a skin round the baked surface) */
+    float   thickness;         /* > 0: a particle deeper than this under the contact surface is left alone */
+    uint32_t flags;            /* 0 */
+    int32_t reserved[3];       /* 0 */
+} sb_distance_field;           /* 48 bytes */
+typedef struct {
+    float a[3];                /* where sample (0,0,0) is, simulation space; also the pivot of ang */
+    float rot[9];              /* rows: the axes ix, iy, iz grow along (orthonormal, not checked) */
+    float lin[3], ang[3];      /* the prop's velocity at a and its angular velocity */
+    float friction, restitution;
+    int32_t reserved[2];       /* 0 */
+} sb_distance_field_pose;      /* 88 bytes */
+/* desc == NULL clears the slot and releases its memory (samples is then not read). SB_ERR_INVALID_ARG (null group; slot outside
+ * 0 .. SB_DISTANCE_FIELD_SLOTS - 1; null samples; a dimension out of range or nx ny nz over SB_DISTANCE_FIELD_MAX_SAMPLES; flags or a
+ * reserved word != 0; a NaN or infinite float of the descriptor; cell <= 0; offset < 0; thickness <= 0; a NaN or infinite sample --
+ * sb_last_error names the first such sample's index --: all checked before the group is touched), SB_ERR_STATE before
+ * sb_group_finalize; a refused call changes nothing and keeps the table set before. */
+int sb_group_set_distance_field(sb_group *g, int32_t slot, const sb_distance_field *desc, const float *samples);
+/* SB_ERR_INVALID_ARG (a null argument; slot out of range; a NaN or infinite field of the pose; friction < 0; restitution outside [0, 1];
+ * a reserved word != 0: all checked before the group is touched), SB_ERR_STATE before sb_group_finalize; a refused call changes nothing. */
+int sb_group_collide_distance_field(sb_group *g, int32_t slot, const sb_distance_field_pose *pose);
+
 /* ---- synchronisation, inspection ------------------------------------------------------------------------------------------------------------ */
 int sb_group_synchronize(sb_group *g);
 int32_t sb_group_rank_count(const sb_group *g);

@@ -106,6 +106,7 @@ struct sb_group {
     std::vector<RankRender> rr;
     int64_t dev_bytes = 0;
     bool heightfield_set = false;                // sb_group_set_heightfield left a table on every rank (SPEC.md 2h)
+    bool distance_field_set[SB_DISTANCE_FIELD_SLOTS] = {};      // sb_group_set_distance_field left a table in this slot on every rank (SPEC.md 2i)
     int32_t reaction_count = 0;                  // the list length of the last sb_group_collide_reactions call (SPEC.md 2g): what a fetch returns
 
     int device_of(int r) const { return devices[(size_t)r]; }
@@ -673,6 +674,36 @@ int sb_group_collide_heightfield(sb_group *g, float friction, float restitution)
     // every rank walks what it holds, ghosts included, and completes its tick (a table that touches nothing too: the ranks stay in the same
     // tick state). The render device takes no part.
     return g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_heightfield_validated(g->ranks[(size_t)r], friction, restitution); }); });
+}
+
+int sb_group_set_distance_field(sb_group *g, int32_t slot, const sb_distance_field *desc, const float *samples) {
+    // null, slot and table checks before the group is touched: refused the same way on a machine without a device
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_set_distance_field: null group");
+    if (int rc = validate_distance_field("sb_group_set_distance_field", slot, desc, samples)) return rc;
+    if (int rc = check_group(g, true, "sb_group_set_distance_field")) return rc;
+    // no rank completes its tick: a table has a lifetime of its own, and a held-back last kernel still fuses with the next tick
+    if (!desc) {
+        if (!g->distance_field_set[slot]) return SB_OK;
+        g->distance_field_set[slot] = false;
+        return g->for_ranks([&](int r) { return guarded([&]() -> int { return clear_distance_field(g->ranks[(size_t)r], slot); }); });
+    }
+    const sb_distance_field D = *desc;
+    g->distance_field_set[slot] = false;      // (set again once every rank has its table: a failure half way leaves no table in force)
+    const int rc = g->for_ranks([&](int r) { return guarded([&]() -> int { return set_distance_field_validated(g->ranks[(size_t)r], slot, D, samples); }); });
+    if (rc) return rc;
+    g->distance_field_set[slot] = true;
+    return SB_OK;
+}
+
+int sb_group_collide_distance_field(sb_group *g, int32_t slot, const sb_distance_field_pose *pose) {
+    if (!g) return fail(SB_ERR_INVALID_ARG, "sb_group_collide_distance_field: null group");
+    if (int rc = validate_distance_field_pose("sb_group_collide_distance_field", slot, pose)) return rc;
+    if (int rc = check_group(g, true, "sb_group_collide_distance_field")) return rc;
+    if (!g->distance_field_set[slot]) return SB_OK;      // nothing at all: no rank completes its tick (sb_group_collide's count == 0)
+    // every rank walks what it holds, ghosts included, and completes its tick (a pose that touches nothing too: the ranks stay in the same
+    // tick state). The render device takes no part.
+    const sb_distance_field_pose P = *pose;
+    return g->for_ranks([&](int r) { return guarded([&]() -> int { return collide_distance_field_validated(g->ranks[(size_t)r], slot, P); }); });
 }
 
 /* ---- render readback, gathered on the render device ------------------------------------------------------------------------------------- */

@@ -329,6 +329,16 @@ struct sb_solver {
     float hf_top = 0.0f;
     bool hf_set = false, hf_in_flight = false;
     sbi::Event ev_hf_read;
+    // Signed-distance volumes (sb_group_set_distance_field, distance_field.hip; SPEC.md 2i), nothing before the first set: per slot the
+    // rank's copy of the samples, the descriptor they came with, and the event recorded behind the last pass that read the slot -- what a
+    // later set or clear of that slot waits for before the memory is written or released. The pose is the call's, never kept.
+    struct DistanceFieldTable {
+        DevBuf<float> d;
+        sb_distance_field desc{};
+        bool set = false, in_flight = false;
+        sbi::Event ev_read;
+    };
+    DistanceFieldTable df[SB_DISTANCE_FIELD_SLOTS];
 
     // The destructor holds only what is ORDER; every handle above gives itself back afterwards (members, in reverse order of declaration,
     // none of which depends on another once the device is idle). sb_destroy has made the solver's device current.
@@ -427,6 +437,13 @@ float heightfield_top(const float *heights, int64_t count);                     
 int set_heightfield_validated(sb_solver *s, const sb_heightfield &d, const float *heights, float top);      // copies; leaves the tick's stream alone
 int clear_heightfield(sb_solver *s);
 int collide_heightfield_validated(sb_solver *s, float friction, float restitution);            // every local particle, ghosts included; asynchronous on s->stream
+
+// ---- distance_field.hip: contacts with signed-distance volumes between two ticks (SPEC.md 2i) ----------------------------------------------
+int validate_distance_field(const char *who, int32_t slot, const sb_distance_field *d, const float *samples);      // slot, descriptor and samples alone (d may be null: a clear); needs neither a group nor a device
+int validate_distance_field_pose(const char *who, int32_t slot, const sb_distance_field_pose *p);
+int set_distance_field_validated(sb_solver *s, int32_t slot, const sb_distance_field &d, const float *samples);    // copies; leaves the tick's stream alone
+int clear_distance_field(sb_solver *s, int32_t slot);
+int collide_distance_field_validated(sb_solver *s, int32_t slot, const sb_distance_field_pose &p);                 // every local particle, ghosts included; asynchronous on s->stream
 
 // ---- abi.hip: the phases of sb_finalize (a group runs them itself) ----------------------------------------------------------------------
 int finalize_local(sb_solver *s);                       // plan + tables, this rank alone (= finalize_plan, then finalize_device)

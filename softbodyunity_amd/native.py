@@ -190,6 +190,49 @@ def heightfield(a, cell, heights2d, rot=None, thickness=1.0):
     return d, h
 
 
+SB_DISTANCE_FIELD_SLOTS, SB_DISTANCE_FIELD_MAX_DIM, SB_DISTANCE_FIELD_MAX_SAMPLES = 4, 1024, 1 << 27
+
+
+class SbDistanceField(C.Structure):
+    """sb_distance_field (48 bytes): the shape of sb_group_set_distance_field's table (SPEC.md 2i). nx, ny, nz: samples along the frame's
+    rows 0, 1, 2, s[(iz * ny + iy) * nx + ix]; cell: the spacing along the rows; offset >= 0: the contact surface is phi = offset;
+    thickness > 0: how deep under it a particle is still pushed out; flags and reserved stay 0"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("cell", C.c_float * 3), ("offset", C.c_float),
+                ("thickness", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
+class SbDistanceFieldPose(C.Structure):
+    """sb_distance_field_pose (88 bytes): where a table stands and how it moves, per call (SPEC.md 2i). a: sample (0, 0, 0) and the pivot
+    of ang; rot: rows = the axes ix, iy, iz grow along; lin, ang: the prop's velocity at a and its angular velocity; reserved stays 0"""
+    _fields_ = [("a", C.c_float * 3), ("rot", C.c_float * 9), ("lin", C.c_float * 3), ("ang", C.c_float * 3), ("friction", C.c_float),
+                ("restitution", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def distance_field(samples3d, cell, offset=0.0, thickness=1.0):
+    """-> (SbDistanceField, samples) as sb_group_set_distance_field takes them. samples3d: (nz, ny, nx), samples3d[iz, iy, ix] signed
+    distances in simulation units, negative inside (mesh.signed_distance_grid bakes them); cell: one spacing or one per axis (ix, iy, iz)."""
+    s = np.ascontiguousarray(samples3d, dtype=np.float32)
+    if s.ndim != 3:
+        raise ValueError("samples3d must be (nz, ny, nx)")
+    d = SbDistanceField()
+    d.nz, d.ny, d.nx = s.shape
+    d.cell[:] = np.broadcast_to(np.asarray(cell, np.float32), (3,)).tolist()
+    d.offset, d.thickness = offset, thickness
+    return d, s
+
+
+def distance_field_pose(a, rot=None, lin=(0, 0, 0), ang=(0, 0, 0), friction=0.0, restitution=0.0):
+    """-> SbDistanceFieldPose for sb_group_collide_distance_field. a: where sample (0, 0, 0) is; rot: (3, 3) with the ROWS the axes ix, iy,
+    iz grow along (None = x, y, z); lin: the prop's velocity at a; ang: its angular velocity about a."""
+    p = SbDistanceFieldPose()
+    p.a[:] = np.asarray(a, np.float32).reshape(3).tolist()
+    p.rot[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1] if rot is None else np.asarray(rot, np.float32).reshape(9).tolist()
+    p.lin[:] = np.asarray(lin, np.float32).reshape(3).tolist()
+    p.ang[:] = np.asarray(ang, np.float32).reshape(3).tolist()
+    p.friction, p.restitution = friction, restitution
+    return p
+
+
 # name -> (restype, argtypes); this table is what tests/test_abi.py checks against include/softbody.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -302,6 +345,8 @@ SIGNATURES = {
     "sb_group_get_collider_reactions": (C.c_int, [_P, C.POINTER(SbColliderReaction), C.c_int32, C.POINTER(C.c_int32)]),
     "sb_group_set_heightfield": (C.c_int, [_P, C.POINTER(SbHeightfield), C.POINTER(C.c_float)]),
     "sb_group_collide_heightfield": (C.c_int, [_P, C.c_float, C.c_float]),
+    "sb_group_set_distance_field": (C.c_int, [_P, C.c_int32, C.POINTER(SbDistanceField), C.POINTER(C.c_float)]),
+    "sb_group_collide_distance_field": (C.c_int, [_P, C.c_int32, C.POINTER(SbDistanceFieldPose)]),
     "sb_group_get_body_state": (C.c_int, [_P, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_body_state_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint32, C.POINTER(SbBodyState)]),
     "sb_group_synchronize": (C.c_int, [_P]),

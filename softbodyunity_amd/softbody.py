@@ -679,6 +679,27 @@ class SoftbodyGroup:
         by Coulomb `friction`. Everything else keeps every bit; with no heightfield set the call does nothing at all."""
         check(native.lib().sb_group_collide_heightfield(self._g, friction, restitution))
 
+    def set_distance_field(self, slot, desc, samples):
+        """Put a prop's signed-distance table into `slot` on every rank's device (sb_group_set_distance_field, SPEC.md 2i): desc and
+        samples as native.distance_field(samples3d, cell, offset, thickness) returns them. Copies; replaces the slot's table; does not
+        complete a held-back tick."""
+        s = np.ascontiguousarray(samples, dtype=np.float32)
+        if s.size != desc.nx * desc.ny * desc.nz:
+            raise ValueError("samples must hold nx * ny * nz values")
+        check(native.lib().sb_group_set_distance_field(self._g, slot, C.byref(desc), s.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def clear_distance_field(self, slot):
+        """Clear `slot` and release its device memory; collide_distance_field on it then does nothing."""
+        check(native.lib().sb_group_set_distance_field(self._g, slot, None, None))
+
+    def collide_distance_field(self, slot, pose):
+        """Resolve the contacts of every particle with the prop in `slot`, standing and moving as `pose` says
+        (native.distance_field_pose), between two ticks, on the devices (sb_group_collide_distance_field, SPEC.md 2i): a particle under
+        the contact surface phi = offset, by less than the table's thickness, is pushed onto it along the field's gradient and, when it
+        approaches the moving prop, loses its normal velocity but for `restitution` and its tangential one by Coulomb `friction`.
+        Everything else keeps every bit; with nothing set in the slot the call does nothing at all."""
+        check(native.lib().sb_group_collide_distance_field(self._g, slot, C.byref(pose)))
+
     def set_render_triangles(self, tri):
         tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
         check(native.lib().sb_group_set_render_triangles(self._g, tri.ctypes.data_as(C.POINTER(C.c_int32)), tri.shape[0]))
