@@ -4,7 +4,9 @@ scripts of tests/frame_sequence_cases.py's fixed slice -- surface forces turned 
 rank holding the whole mesh (the automatic partition) and with ranks holding windows (SB_PARTITION_BLOCKS). Every observation is compared
 with the reference driver's as on one rank; of the counters ticks_fused must agree on every rank and with the model, and
 ticks_fused_kinematic is the largest of the ranks' (a rank that owns none of the targets carries none along: its set_kinematic returns
-early, and a state-changing call behind the move must still complete its tick).
+early, and a state-changing call behind the move must still complete its tick). A fourth leg per case comes from the slice's second block:
+a kinematic move right in front of a collide_distance_field on a full slot (SPEC.md 2i) -- the table copied to every rank, ghosts treated by
+their holder, and every rank's tick completed whether or not it owns a pin.
 Prints `FRAME GROUP OK ...` or `FRAME GROUP MISMATCH ...`.
 
 usage: frame_group_case.py <threads|walk> <ranks>
@@ -30,9 +32,23 @@ def scripts_for(case):
         names = [fc.coverage_name(n, a) for n, a in sc["script"]]
         if sc["body"] in moved and any(p == "set_kinematic_positions" and q in fc.STATE_CHANGING for p, q in zip(names, names[1:])):
             moved[sc["body"]].append(seed)
+    # ... and of the second block one in which the move stands right in front of a signed-distance call on a full slot: cases 0 and 2 on the
+    # 16-cube with the automatic partition, cases 1 and 3 on the 10-cube in windows
+    props = {"cube16": [], "cube10": []}
+    for seed in fc.SECOND_BLOCK[:fc.N2_PAIRS + fc.N2_PLANTED]:
+        sc = fc.make_scenario(seed)
+        full = set()
+        for k, (name, a) in enumerate(sc["script"]):
+            if name == "set_distance_field":
+                full.add(a["slot"])
+            elif name == "clear_distance_field":
+                full.discard(a["slot"])
+            elif name == fc.D and a["slot"] in full and sc["script"][k - 1][0] == "set_kinematic_positions" and sc["body"] in props and seed not in props[sc["body"]]:
+                props[sc["body"]].append(seed)
+    prop = (props["cube10"][case // 2], native.SB_PARTITION_BLOCKS) if case % 2 else (props["cube16"][case // 2], native.SB_PARTITION_AUTO)
     # the 16-cube's pins are one edge, which the last rank owns alone under either partition: the early return of set_kinematic on the others
     return [(moved["cube16"][case], native.SB_PARTITION_AUTO), (moved["cube10"][case], native.SB_PARTITION_BLOCKS),
-            (fc.N_PAIRS + fc.N_PLANTED + case, native.SB_PARTITION_AUTO)]
+            (fc.N_PAIRS + fc.N_PLANTED + case, native.SB_PARTITION_AUTO), prop]
 
 
 def main(host, ranks):

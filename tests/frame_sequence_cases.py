@@ -17,8 +17,14 @@ What the reference takes from SPEC.md and include/softbody.h:
   2d  placement maps every particle, pinned ones (and so the moved pins) included unless KEEP_PINNED
   2e  surface forces need render triangles, one rank and no embedding (SB_ERR_UNSUPPORTED otherwise)
   2f  colliders leave w = 0 alone (the moved pins too); 2g at most SB_COLLIDE_REACTIONS_MAX colliders; 2h the heightfield likewise
+  2i  a signed-distance table lives in a slot with a lifetime of its own: set, replace and clear complete nothing, a call on a full slot
+      completes the tick, a call on an empty slot does nothing at all (softbody_group.h: "the tick stays held back")
   6a-6d a snapshot is the state at ITS readback_begin; 6e, 6g queries answer for the snapshot ended last; 6f POSE reads positions only
-The counters are predicted by TickModel, from begin_tick / flush_deferred / can_peek (csrc/schedule.hip) as softbody.h states them."""
+The counters are predicted by TickModel, from begin_tick / flush_deferred / can_peek (csrc/schedule.hip) as softbody.h states them.
+
+The fixed slice has two blocks. FIRST_BLOCK (seeds 0 .. 199) was written before the signed-distance volumes and stays byte for byte what
+it was (tests/golden/frame_slice_v1.sha256.txt): its generator draws no distance-field step. SECOND_BLOCK (seeds 200 .. 279) and every
+seed behind it use the extended generator, in which collide_distance_field is one more call that must complete the tick."""
 import functools
 import json
 import os
@@ -36,6 +42,8 @@ import bounds_ref                            # noqa: E402
 import closest_ref                           # noqa: E402
 import collider_reaction_ref                 # noqa: E402
 import collider_ref                          # noqa: E402
+import distance_field_cases                  # noqa: E402
+import distance_field_ref                    # noqa: E402
 import heightfield_cases                     # noqa: E402
 import heightfield_ref                       # noqa: E402
 import impulse_ref                           # noqa: E402
@@ -60,7 +68,18 @@ TICK_SHAPES = ("same", "other even S", "odd S", "other dt")
 N_PAIRS = len(STATE_CHANGING) ** 2
 N_PLANTED = len(STATE_CHANGING) * 4
 N_RANDOM = 60
-FIXED_SLICE = tuple(range(N_PAIRS + N_PLANTED + N_RANDOM))
+FIRST_BLOCK = tuple(range(N_PAIRS + N_PLANTED + N_RANDOM))
+# the second block: the signed-distance calls (SPEC.md 2i) against everything above. D on a FULL slot must complete the tick.
+D = "collide_distance_field"
+ALL = STATE_CHANGING + (D,)
+DF_SLOTS = 4
+DF_PAIRS = tuple(p for X in STATE_CHANGING for p in ((D, X), (X, D))) + ((D, D),)
+DF_LIFETIMES = ("a set between two ticks", "a replacement of equal size right behind a call", "a replacement of another size right behind a call",
+                "a clear right behind a call, then a collide on the slot now empty", "a collide on an empty slot beside a full one",
+                "one slot at two poses and a second slot behind colliders and terrain", "a snapshot pending across the call")
+N2_PAIRS, N2_PLANTED, N2_LIFETIMES, N2_RANDOM = len(DF_PAIRS), 4, len(DF_LIFETIMES), 48
+SECOND_BLOCK = tuple(range(len(FIRST_BLOCK), len(FIRST_BLOCK) + N2_PAIRS + N2_PLANTED + N2_LIFETIMES + N2_RANDOM))
+FIXED_SLICE = FIRST_BLOCK + SECOND_BLOCK
 CHUNK = 8                                    # scenarios per parametrised chunk: see tests/test_frame_sequences.py for the measured reference time
 
 
@@ -166,6 +185,7 @@ class TickModel:
     def __init__(self, peeking, tiled=True):
         self.peeking, self.tiled = bool(peeking), bool(tiled)
         self.deferred, self.S, self.dt, self.kin = False, None, None, False
+        self.slots = set()                   # the signed-distance slots that hold a table
         self.fused = self.kin_fused = self.peeks = 0
 
     def counters(self):
@@ -201,6 +221,22 @@ class TickModel:
     def nothing(self):
         pass
 
+    # signed-distance slots (softbody_group.h): a table has a lifetime of its own -- a set, a replacement and a clear complete nothing;
+    # a call completes the tick where the slot holds a table and "does nothing at all (the tick stays held back)" where it holds none
+    def set_distance_field(self, slot):
+        self.slots.add(slot)
+        self.nothing()
+
+    def clear_distance_field(self, slot):
+        self.slots.discard(slot)
+        self.nothing()
+
+    def collide_distance_field(self, slot):
+        if slot in self.slots:
+            self.complete()
+        else:
+            self.nothing()
+
 
 # ---- arguments -> the records both drivers use -----------------------------------------------------------------------------------------------
 
@@ -223,6 +259,22 @@ def _heightfield(a):
     hf = heightfield_cases.ticking_field(a["lo"], a["hi"])
     hf["h"] = (hf["h"] * F(a["scale"]) + F(a["lift"])).astype(np.float32)
     return hf
+
+
+def _distance_field(a):
+    """-> (table, side): the prop of a set_distance_field step, a pure function of its arguments. "sphere": |p| - radius on n^3 samples
+    (distance_field_cases.sampled_sphere); "floor": the plane field phi = y - y0 about the table's middle on 3^3 samples, with a thick band"""
+    if a["prop"] == "sphere":
+        return distance_field_cases.sampled_sphere(a["radius"], a["n"], thickness=a["thickness"])
+    assert a["prop"] == "floor", a["prop"]
+    side = float(a["side"])
+    y = side / 2 * np.arange(3) - side / 2 - a["y0"]
+    return distance_field_ref.make(np.broadcast_to(y[None, :, None], (3, 3, 3)), side / 2, 0.0, a["thickness"]), side
+
+
+def _pose(a, side):
+    """the pose of a collide_distance_field step for the table in its slot (any side where the slot is empty: nothing reads it)"""
+    return distance_field_cases.pose_about(a["centre"], side, a["quat"], lin=a["lin"], ang=a["ang"], friction=a["friction"], restitution=a["restitution"])
 
 
 def _placement(a):
@@ -301,6 +353,8 @@ def _refusal_expected(sc, what, pending, world):
         return SB_ERR_INVALID_ARG if b["mesh"].inv_mass[_free_particle(b)] != 0 else None
     if what == "step_dt_zero":
         return SB_ERR_INVALID_ARG
+    if what in ("distance_field_slot_4", "distance_field_restitution"):
+        return SB_ERR_INVALID_ARG
     raise ValueError(what)
 
 
@@ -345,15 +399,17 @@ def run_reference(oracle_mod, sc, world=1, info=None):
     pins = PinTracker(b)
     obs = []
     pending, ended, hits, hf, react = [], None, None, None, None
+    tables = {}                              # signed-distance slot -> (table, side)
     info = {} if info is None else info
-    info.update(contact_hits=[], velocity_changed=[], refusals=[], call_left=[], call_shape=[])
+    info.update(contact_hits=[], distance_field_hits=[], velocity_changed=[], refusals=[], call_left=[], call_shape=[])
     awaiting, last_tick, peeked, by_velocity_read = [], None, False, False
     tri_kw = dict(tri=b["etri"], cage=b["cage"], w4=b["w4"]) if sc["mode"] == "embedding" else dict(tri=b["tri"])
 
     for k, (name, a) in enumerate(sc["script"]):
         lab = f"step {k} {name}"
         cov = coverage_name(name, a)
-        if cov in STATE_CHANGING:            # what the call meets, and (once the next tick comes) what shape of tick it stands in front of
+        completes = cov in STATE_CHANGING or (cov == D and a["slot"] in tables)
+        if completes:                        # what the call meets, and (once the next tick comes) what shape of tick it stands in front of
             left = (LEFT_STATES[3] if model.deferred and model.kin else LEFT_STATES[0] if model.deferred and peeked else LEFT_STATES[1] if model.deferred
                     else LEFT_STATES[2] if by_velocity_read else None)
             info["call_left"].append((cov, left))
@@ -398,6 +454,18 @@ def run_reference(oracle_mod, sc, world=1, info=None):
             hf = _heightfield(a)
         elif name == "clear_heightfield":
             hf = None
+        elif name == "set_distance_field":
+            tables[a["slot"]] = _distance_field(a)
+            model.set_distance_field(a["slot"])
+        elif name == "clear_distance_field":
+            tables.pop(a["slot"], None)
+            model.clear_distance_field(a["slot"])
+        elif name == "collide_distance_field":
+            if a["slot"] in tables:          # (on an empty slot the call does nothing at all: softbody_group.h)
+                df, side = tables[a["slot"]]
+                h = distance_field_ref.apply(o.x, o.v, o.w, df, _pose(a, side))
+                info["contact_hits"].append(int(h.sum())); info["distance_field_hits"].append(int(h.sum()))
+            model.collide_distance_field(a["slot"])
         elif name == "set_state":
             x, v = _state(b, a)
             o.x[:] = x; o.v[:] = v; pins.set_state(x)
@@ -447,7 +515,7 @@ def run_reference(oracle_mod, sc, world=1, info=None):
             raise ValueError(f"unknown step {name}")
         if name in ("get_positions", "get_bounds", "readback_begin") or (name == "get_body_state" and a["what"] == POSE):
             peeked = model.deferred
-        by_velocity_read = (name == "get_velocities") or (by_velocity_read and not model.deferred and cov not in STATE_CHANGING)
+        by_velocity_read = (name == "get_velocities") or (by_velocity_read and not model.deferred and not completes)
         obs.append(("counters", lab, model.counters()))
     info["final"] = (o.x.copy(), o.v.copy())
     return obs
@@ -530,6 +598,7 @@ def run_group(g, sc, upto=None):
     pins = PinTracker(b)
     obs = []
     hits, n_pending = None, 0
+    sides = {}                               # signed-distance slot -> the side of its table (the pose is built from it)
     W = len(g.devices)
     for k, (name, a) in enumerate(sc["script"][:upto]):
         lab = f"step {k} {name}"
@@ -557,6 +626,13 @@ def run_group(g, sc, upto=None):
             g.set_heightfield(*heightfield_ref.to_native(_heightfield(a)))
         elif name == "clear_heightfield":
             g.clear_heightfield()
+        elif name == "set_distance_field":
+            df, sides[a["slot"]] = _distance_field(a)
+            g.set_distance_field(a["slot"], *distance_field_ref.to_native(df))
+        elif name == "clear_distance_field":
+            g.clear_distance_field(a["slot"]); sides.pop(a["slot"], None)
+        elif name == "collide_distance_field":
+            g.collide_distance_field(a["slot"], distance_field_ref.pose_to_native(_pose(a, sides.get(a["slot"], 1.0))))
         elif name == "set_state":
             x, v = _state(b, a)
             g.set_state(x, v); pins.set_state(x)
@@ -603,6 +679,11 @@ def run_group(g, sc, upto=None):
                 rc = _status(lambda: g.set_kinematic_positions(np.array([_free_particle(b)], np.int32), np.zeros((1, 3), np.float32)))
             elif what == "step_dt_zero":
                 rc = _status(lambda: g.step(0.0, 4))
+            elif what == "distance_field_slot_4":
+                rc = _status(lambda: g.collide_distance_field(DF_SLOTS, distance_field_ref.pose_to_native(_pose(a["pose"], 1.0))))
+            elif what == "distance_field_restitution":      # on a full slot: refused before the table is looked at
+                assert a["slot"] in sides and a["pose"]["restitution"] == 1.5
+                rc = _status(lambda: g.collide_distance_field(a["slot"], distance_field_ref.pose_to_native(_pose(a["pose"], sides[a["slot"]]))))
             else:
                 raise ValueError(what)
             obs.append(("status", lab + " " + what, rc))
@@ -708,6 +789,7 @@ class _Gen:
         self.shift = np.zeros(3)
         self.dt, self.S = b["dt"], b["S"]
         self.reacted = self.refused = False
+        self.df = {}                         # signed-distance slot -> the arguments of the set that filled it
 
     # -- geometry
     def box(self):
@@ -821,6 +903,73 @@ class _Gen:
             self.set_heightfield()
         self.add("collide_heightfield", friction=_r(self.rng.uniform(0, 0.8)), restitution=_r(self.rng.uniform(0, 0.5)))
 
+    # -- signed-distance props (SPEC.md 2i): sized and placed from box(), as colliders() does
+    def set_distance_field(self, slot=None, size=None, prop=None):
+        """a table into `slot` (drawn where None). Over a full slot this is a replacement: size "same" keeps the sample count, so the memory
+        is written over; "other" changes it, so the old table is released (drawn where None). `prop` names the prop of an empty slot."""
+        rng = self.rng
+        lo, hi = self.box()
+        ext = hi - lo
+        slot = int(rng.integers(0, DF_SLOTS)) if slot is None else slot
+        old, n = self.df.get(slot), None
+        if old is not None:
+            size = size or ("same", "other")[int(rng.integers(0, 2))]
+            if size == "same":
+                prop, n = old["prop"], old.get("n")
+            elif old["prop"] == "floor":
+                prop = "sphere"
+            elif rng.random() < 0.5:
+                prop, n = "sphere", 26 - old["n"]      # 9 <-> 17
+            else:
+                prop = "floor"
+        prop = prop or ("sphere", "floor")[int(rng.integers(0, 2))]
+        if prop == "sphere":
+            radius = (0.2 * float(ext.max()) if self.b["kind"] == "cloth" else 0.3 * float(min(ext[0], ext[2]))) * float(rng.uniform(0.9, 1.1))
+            a = dict(slot=slot, prop="sphere", radius=_r(radius), n=int(n or rng.choice([9, 17])), thickness=_r(0.6 * radius))
+        else:
+            up = max(float(ext.max()), 1.0)
+            a = dict(slot=slot, prop="floor", side=_r(4.0 * up), y0=_r(rng.uniform(-0.01, 0.01) * max(float(ext[1]), 1.0)), thickness=_r(2.0 * up))
+        self.add("set_distance_field", **a)
+        self.df[slot] = a
+
+    def clear_distance_field(self, slot):
+        self.add("clear_distance_field", slot=slot)
+        self.df.pop(slot, None)
+
+    def df_pose(self, slot):
+        """where the prop of `slot` goes: the sphere with its cap in the body's underside (under the cloth only the cap pokes through), the
+        floor a little above the body's lowest point; at rest or moving, half and half"""
+        rng = self.rng
+        lo, hi = self.box()
+        mid, ext = (lo + hi) / 2, hi - lo
+        t = self.df.get(slot, dict(prop="sphere", radius=1.0))
+        up = max(float(ext[1]), 1.0)
+        if t["prop"] == "sphere":
+            radius = t["radius"]
+            cy = lo[1] - 0.85 * radius if self.b["kind"] == "cloth" else lo[1] - radius + 0.12 * ext[1]
+            centre = np.array([mid[0], cy, mid[2]]) + rng.uniform(-0.04, 0.04, 3) * np.array([ext[0], 0.25 * up, ext[2]])
+            quat = np.concatenate([rng.uniform(-0.5, 0.5, 3), [1.0]])
+        else:
+            centre = np.array([mid[0], lo[1] + 0.05 * up, mid[2]]) + rng.uniform(-0.02, 0.02, 3) * np.array([ext[0], 0.25 * up, ext[2]])
+            quat = np.concatenate([rng.uniform(-0.02, 0.02, 3), [1.0]])
+        moving = bool(rng.integers(0, 2))
+        lin = [0.0, 0.1 * up, 0.0] + rng.uniform(-0.05, 0.05, 3) * up if moving else np.zeros(3)
+        ang = rng.uniform(-0.2, 0.2, 3) if moving else np.zeros(3)
+        return dict(centre=_v(centre), quat=_v(quat), lin=_v(lin), ang=_v(ang), friction=_r(rng.uniform(0, 0.8)), restitution=_r(rng.uniform(0, 0.5)))
+
+    def collide_distance_field(self, slot=None, empty=False):
+        """a call on a full slot (one is filled where none is); with `empty`, on a slot that holds nothing (where there is one)"""
+        rng = self.rng
+        free = [s for s in range(DF_SLOTS) if s not in self.df]
+        if slot is None and empty and free:
+            slot = free[int(rng.integers(0, len(free)))]
+        elif slot is None:
+            if not self.df:
+                self.set_distance_field()
+            full = sorted(self.df)
+            slot = full[int(rng.integers(0, len(full)))]
+        self.add("collide_distance_field", slot=slot, **self.df_pose(slot))
+
     def set_state(self):
         self.add("set_state", seed=int(self.rng.integers(0, 2 ** 31)), shift=_v(self.shift), dx=0.02, dv=0.4)
 
@@ -870,7 +1019,16 @@ class _Gen:
             self.add("collider_reactions", twice=bool(twice))
 
     def refuse(self, what):
-        self.add("refuse", what=what); self.refused = True
+        if what == "distance_field_slot_4":              # a valid pose on the slot behind the last
+            self.add("refuse", what=what, pose=self.df_pose(0))
+        elif what == "distance_field_restitution":       # restitution 1.5 on a full slot
+            if not self.df:
+                self.set_distance_field()
+            slot = sorted(self.df)[int(self.rng.integers(0, len(self.df)))]
+            self.add("refuse", what=what, slot=slot, pose=dict(self.df_pose(slot), restitution=1.5))
+        else:
+            self.add("refuse", what=what)
+        self.refused = True
 
     def reads(self):
         self.add("get_positions"); self.add("get_velocities")
@@ -895,9 +1053,12 @@ def _config(seed, rng, body_kind=None, mode=None, peek0=None):
 _REFUSALS = ("reactions_1025", "third_snapshot", "kinematic_free_particle", "step_dt_zero", "surface_forces_embedding")
 
 
-def _plant_refusal(G, rng):
+_REFUSALS_2 = _REFUSALS + ("distance_field_slot_4", "distance_field_restitution")      # drawn from for seeds behind the first block
+
+
+def _plant_refusal(G, rng, refusals=_REFUSALS):
     """one refusal per scenario, where it IS one: a third snapshot needs two pending, the surface forces an embedding"""
-    what = str(rng.choice(_REFUSALS))
+    what = str(rng.choice(refusals))
     if G.refused:
         return
     if G.sc["mode"] == "embedding" and rng.random() < 0.5:
@@ -910,10 +1071,230 @@ def _plant_refusal(G, rng):
     G.refuse(what)
 
 
+def _random_script(G, rng, sc, extended):
+    """the randomly drawn script. `extended` (every seed behind the first block): state-changing calls are drawn from ALL -- a call on a
+    slot that holds nothing one time in four --, the branch that sets or clears the heightfield is shared evenly with set / replace / clear
+    of a signed-distance slot, and the refusal is drawn from the extended list. Without it not one draw differs from what the first block
+    was generated with."""
+    calls, refusals = (ALL, _REFUSALS_2) if extended else (STATE_CHANGING, _REFUSALS)
+    frames = int(rng.integers(4, 8))
+    refusal_at = int(rng.integers(0, frames))
+    late_fetch = False
+    for f in range(frames):
+        n_between = int(rng.integers(0, 4))
+        for _ in range(n_between):
+            r = rng.random()
+            if r < 0.55:
+                call = str(rng.choice(calls))
+                if call == D:
+                    G.collide_distance_field(empty=rng.random() < 0.25)
+                else:
+                    G.call(call)
+                if call == "collide_with_reactions":
+                    if rng.random() < 0.5:
+                        G.fetch(twice=rng.random() < 0.5)
+                    else:
+                        late_fetch = True
+            elif r < 0.7:
+                G.kinematic(twice=rng.random() < 0.3)
+            elif r < 0.8:
+                if extended and rng.random() < 0.5:
+                    slot = int(rng.integers(0, DF_SLOTS))
+                    if slot in G.df and rng.random() < 0.4:
+                        G.clear_distance_field(slot)
+                    else:
+                        G.set_distance_field(slot)                                        # (a replacement where the slot is full)
+                elif G.hf and rng.random() < 0.6:
+                    G.add("clear_heightfield"); G.hf = False
+                else:
+                    G.set_heightfield(scale=float(rng.choice([1.0, 1.5, 0.5])))      # (a replacement, where one is set, right behind a call)
+            elif r < 0.9:
+                G.add(str(rng.choice(["get_positions", "get_bounds"])))
+            else:
+                G.add("get_body_state", what=POSE)
+        if f == refusal_at:
+            _plant_refusal(G, rng, refusals)
+        G.tick(str(rng.choice(TICK_SHAPES, p=[0.55, 0.15, 0.15, 0.15])))
+        if late_fetch:
+            G.fetch(twice=rng.random() < 0.5); late_fetch = False
+        r = rng.random()
+        if r < 0.35 and G.pending < 2:      # ended at once
+            G.begin(); G.end()
+        elif r < 0.7:                        # pipelined: at most two pending, the oldest ended first
+            if G.pending == 2:
+                G.end()
+            G.begin()
+        elif G.pending and rng.random() < 0.5:
+            G.end()
+        if G.ended and rng.random() < 0.5:
+            G.query()
+        if sc["every_tick"]:
+            G.reads()
+    G.finish()
+
+
+def _second_block_scenario(seed, rng):
+    """Seeds behind the first block. N2_PAIRS scenarios: (D, X) and (X, D) for each of the ten calls of STATE_CHANGING and (D, D) on two
+    slots, in the shape of the first block's pairs -- the table set before the first tick -- and closed by what happens to a prop sooner or
+    later: it is replaced (even j) or cleared and called once more (odd j) right behind a call. N2_PLANTED: D behind each left state, in
+    front of each tick shape. N2_LIFETIMES: DF_LIFETIMES, the tick held back (every body's S is even); sc["leaves_held_back"] lists the
+    steps that must not complete it, each with nothing but such steps between it and the next tick, which therefore fuses. All others: the
+    random generator, extended."""
+    j = seed - len(FIRST_BLOCK)
+    if j < N2_PAIRS:
+        A, B = DF_PAIRS[j]
+        mode = ["full", "render_set"][j % 2] if "surface_forces" in (A, B) else None
+        # (every sixth scenario moves the pins right in front of D on a lattice body: tests/frame_group_case.py cuts windows from those)
+        sc = _config(seed, rng, BODIES[(j // 6) % 2] if j % 6 == 0 else BODIES[(j + j // 4) % 4], mode)
+        sc["plan"] = f"pair {A} -> {B}"
+        G = _Gen(seed, rng, body(sc["body"]), sc)
+        if "collide_heightfield" in (A, B):
+            G.set_heightfield()
+        slots = [j % DF_SLOTS, (j + 1 + j // DF_SLOTS % 3) % DF_SLOTS]
+        G.set_distance_field(slots[0], prop=("sphere", "floor")[j % 2])
+        if (A, B) == (D, D):
+            G.set_distance_field(slots[1], prop="floor")
+        G.tick(); G.tick()
+        if "impulse_surface" in (A, B):
+            G.need_hits()
+        if sc["every_tick"]:
+            G.add("get_positions")
+        if j % 3 == 0 and len(G.b["pins"]):
+            G.kinematic()
+        for k, c in enumerate((A, B)):
+            if c == D:
+                G.collide_distance_field(slots[k] if (A, B) == (D, D) else slots[0])
+            else:
+                G.call(c, j + k)
+        if "collide_with_reactions" in (A, B):
+            G.fetch(twice=j % 2 == 0)
+        G.tick(); G.tick()
+        G.collide_distance_field(slots[0])
+        if j % 2 == 0:
+            G.set_distance_field(slots[0], size=("same", "other")[j // 2 % 2])
+            G.collide_distance_field(slots[0])
+        else:
+            G.clear_distance_field(slots[0])
+            G.collide_distance_field(slots[0])
+        _plant_refusal(G, rng, _REFUSALS_2)
+        G.tick()
+        G.finish()
+    elif j < N2_PAIRS + N2_PLANTED:
+        k = j - N2_PAIRS
+        left, shape = LEFT_STATES[k], TICK_SHAPES[(k + 1) % 4]
+        sc = _config(seed, rng, BODIES[(k + 1) % 4], None, peek0=True if k == 0 else None)
+        sc["plan"] = f"{D} behind '{left}', in front of a tick of shape '{shape}'"
+        G = _Gen(seed, rng, body(sc["body"]), sc)
+        G.set_distance_field(k, prop=("sphere", "floor")[k % 2])
+        G.tick(); G.tick()
+        if k == 0:
+            G.add("get_positions")
+        elif k == 2:
+            G.add("get_velocities")
+        elif k == 3:
+            G.kinematic()
+        G.collide_distance_field(k)
+        G.tick(shape); G.tick()
+        _plant_refusal(G, rng, _REFUSALS_2)
+        G.tick()
+        G.finish()
+    elif j < N2_PAIRS + N2_PLANTED + N2_LIFETIMES:
+        k = j - N2_PAIRS - N2_PLANTED
+        sc = _config(seed, rng, BODIES[k % 4], None)
+        sc["plan"] = "table lifetime: " + DF_LIFETIMES[k]
+        G = _Gen(seed, rng, body(sc["body"]), sc)
+        held = []                            # the steps that must leave the tick held back
+        s0, s1 = k % DF_SLOTS, (k + 2) % DF_SLOTS
+
+        def quiet(fn, *a, **kw):
+            fn(*a, **kw); held.append(len(G.script) - 1)
+        if k == 0:
+            G.tick(); G.tick()
+            quiet(G.set_distance_field, s0, prop="sphere")
+            G.tick(); G.tick()
+            G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            quiet(G.set_distance_field, s0, size="other")      # (nothing reads the slot any more: the tick stays held back all the same)
+            G.tick()
+        elif k in (1, 2):
+            G.set_distance_field(s0, prop=("floor", "sphere")[k - 1])
+            G.tick(); G.tick()
+            G.collide_distance_field(s0)
+            G.set_distance_field(s0, size=("same", "other")[k - 1])
+            G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            quiet(G.set_distance_field, s0, size=("same", "other")[k - 1])      # the pass before is long done: the wait finds nothing
+            G.tick()
+            G.collide_distance_field(s0)
+        elif k == 3:
+            G.set_distance_field(s0, prop="sphere")
+            G.tick(); G.tick()
+            G.collide_distance_field(s0)
+            G.clear_distance_field(s0)
+            G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            G.set_distance_field(s0, prop="floor")
+            G.tick()
+            G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            quiet(G.clear_distance_field, s0)
+            quiet(G.collide_distance_field, s0)
+            G.tick()
+        elif k == 4:
+            G.set_distance_field(s0, prop="floor")
+            G.tick(); G.tick()
+            quiet(G.collide_distance_field, s1)
+            G.tick()
+            quiet(G.collide_distance_field, s1)
+            G.tick()
+            G.collide_distance_field(s1); G.collide_distance_field(s0)
+            G.tick(); G.tick()
+            G.collide_distance_field(s0); G.collide_distance_field(s1)
+        elif k == 5:                         # the order of csharp/Softbody.cs: colliders, terrain, then props
+            G.set_heightfield()
+            G.set_distance_field(s0, prop="sphere"); G.set_distance_field(s1, prop="floor")
+            G.tick(); G.tick()
+            for _ in range(2):
+                G.collide_with_reactions(); G.collide_heightfield()
+                G.collide_distance_field(s0); G.collide_distance_field(s0); G.collide_distance_field(s1)
+                G.fetch()
+                G.tick()
+        else:                                # the snapshot is the state at ITS readback_begin
+            G.set_distance_field(s0, prop="sphere")
+            G.tick(); G.tick()
+            G.begin()
+            G.collide_distance_field(s0)
+            G.end()
+            G.query("raycast"); G.query("closest_points")
+            G.tick()
+            G.begin()
+            G.collide_distance_field(s0)
+            G.tick()
+            G.end()
+            G.query("closest_points"); G.query("raycast")
+        G.tick(); G.tick()
+        _plant_refusal(G, rng, _REFUSALS_2)
+        G.tick()
+        G.finish()
+        sc["leaves_held_back"] = held
+    else:
+        sc = _config(seed, rng)
+        sc["plan"] = "random"
+        G = _Gen(seed, rng, body(sc["body"]), sc)
+        _random_script(G, rng, sc, extended=True)
+    sc["script"] = G.script
+    return sc
+
+
 def make_scenario(seed):
     """The scenario of a seed. 0 .. N_PAIRS-1: the ordered pair (A, B) of state-changing calls back to back in one frame; the next N_PLANTED:
-    each call behind each state the last tick can have left, and in front of each tick shape; all others drawn at random."""
+    each call behind each state the last tick can have left, and in front of each tick shape; the rest of FIRST_BLOCK drawn at random, without
+    a signed-distance step. Every seed behind FIRST_BLOCK: _second_block_scenario."""
     rng = np.random.default_rng([20250611, int(seed)])
+    if seed >= len(FIRST_BLOCK):
+        return _second_block_scenario(seed, rng)
     nC = len(STATE_CHANGING)
     if seed < N_PAIRS:
         A, B = STATE_CHANGING[seed // nC], STATE_CHANGING[seed % nC]
@@ -969,51 +1350,7 @@ def make_scenario(seed):
         sc = _config(seed, rng)
         sc["plan"] = "random"
         G = _Gen(seed, rng, body(sc["body"]), sc)
-        frames = int(rng.integers(4, 8))
-        refusal_at = int(rng.integers(0, frames))
-        late_fetch = False
-        for f in range(frames):
-            n_between = int(rng.integers(0, 4))
-            for _ in range(n_between):
-                r = rng.random()
-                if r < 0.55:
-                    call = str(rng.choice(STATE_CHANGING))
-                    G.call(call)
-                    if call == "collide_with_reactions":
-                        if rng.random() < 0.5:
-                            G.fetch(twice=rng.random() < 0.5)
-                        else:
-                            late_fetch = True
-                elif r < 0.7:
-                    G.kinematic(twice=rng.random() < 0.3)
-                elif r < 0.8:
-                    if G.hf and rng.random() < 0.6:
-                        G.add("clear_heightfield"); G.hf = False
-                    else:
-                        G.set_heightfield(scale=float(rng.choice([1.0, 1.5, 0.5])))      # (a replacement, where one is set, right behind a call)
-                elif r < 0.9:
-                    G.add(str(rng.choice(["get_positions", "get_bounds"])))
-                else:
-                    G.add("get_body_state", what=POSE)
-            if f == refusal_at:
-                _plant_refusal(G, rng)
-            G.tick(str(rng.choice(TICK_SHAPES, p=[0.55, 0.15, 0.15, 0.15])))
-            if late_fetch:
-                G.fetch(twice=rng.random() < 0.5); late_fetch = False
-            r = rng.random()
-            if r < 0.35 and G.pending < 2:      # ended at once
-                G.begin(); G.end()
-            elif r < 0.7:                        # pipelined: at most two pending, the oldest ended first
-                if G.pending == 2:
-                    G.end()
-                G.begin()
-            elif G.pending and rng.random() < 0.5:
-                G.end()
-            if G.ended and rng.random() < 0.5:
-                G.query()
-            if sc["every_tick"]:
-                G.reads()
-        G.finish()
+        _random_script(G, rng, sc, extended=False)
     sc["script"] = G.script
     return sc
 

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Randomised differential test of FRAME SEQUENCES: the open-ended form of tests/test_gpu_frame_sequences.py. Every seed is a scenario of
 tests/frame_sequence_cases.py -- a small body, a render mode, and a script that interleaves every between-tick call of the group API
-(impulses, placement, surface forces, collider and heightfield contacts, reactions, state queries, kinematic moves, readbacks, ray casts,
-closest points) with ticks of changing shape -- walked on a SoftbodyGroup of one rank and on the CPU oracle with the tests/*_ref.py
-modules; every observation is compared under its rule, the sb_stats counters against the counter model. Seeds 0 .. 199 are the fixed
-slice pytest runs; the default start lies behind them.
+(impulses, placement, surface forces, collider, heightfield and signed-distance contacts with the tables' set / replace / clear, reactions,
+state queries, kinematic moves, readbacks, ray casts, closest points) with ticks of changing shape -- walked on a SoftbodyGroup of one rank and on the CPU oracle with the tests/*_ref.py
+modules; every observation is compared under its rule, the sb_stats counters against the counter model. Seeds 0 .. 279 are the fixed
+slice pytest runs (0 .. 199 its first block, generated without a signed-distance step; every seed from 200 on draws them too); the default
+start lies behind them.
 
 One child process per batch of scenarios. The child exits on the first HIP error, and after a child that died abnormally the parent
 starts nothing further (a GPU fault is a finding to read, not to run again).

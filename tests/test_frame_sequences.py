@@ -6,31 +6,46 @@ finite and moving, that planted refusals are refusals, that a printed script rep
 Measured here (one x86 core): the reference driver takes 4.1 s for the 200 scenarios of the slice, 0.02 s per scenario on average and
 0.16 s for the slowest (seed 194: a 16^3 cube with surface forces, whose reference is a Python loop over 2 700 triangles); building the
 four bodies once costs about 1 s. A chunk of frame_sequence_cases.CHUNK = 8 scenarios therefore costs the GPU module about 0.2 s of
-reference, 1.3 s at the very worst, and less than that on the GPU side."""
+reference, 1.3 s at the very worst, and less than that on the GPU side.
+The second block (seeds 200 .. 279, the signed-distance calls; tables of 9^3 and 17^3 samples): 3.2 s for its 80 scenarios, 0.04 s on
+average and 0.27 s for the slowest (seed 268: the 16^3 cube again, with two surface-force calls -- the Python loop, not its table), 1.7 times the
+first block's slowest."""
 import collections
+import hashlib
+import os
 import time
 
 import numpy as np
 import pytest
 
 import frame_sequence_cases as fc
-from frame_sequence_cases import LEFT_STATES, STATE_CHANGING, TICK_SHAPES, TickModel
+from frame_sequence_cases import ALL, LEFT_STATES, STATE_CHANGING, TICK_SHAPES, D, TickModel
 
 
-@pytest.fixture(scope="module")
-def slice_(oracle_mod):
-    """every scenario of the fixed slice with the reference's observations and what the driver noted about it; computed once"""
+def _walk_block(oracle_mod, seeds):
     assert fc.constants_match()
     out, seconds = [], []
-    for seed in fc.FIXED_SLICE:
+    for seed in seeds:
         sc = fc.make_scenario(seed)
         info = {}
         t0 = time.perf_counter()
         obs = fc.run_reference(oracle_mod, sc, info=info)
         seconds.append(time.perf_counter() - t0)
         out.append((sc, obs, info))
-    print(f"reference: {sum(seconds):.1f} s for {len(out)} scenarios, mean {np.mean(seconds):.3f} s, slowest {max(seconds):.2f} s (seed {int(np.argmax(seconds))})")
+    print(f"reference: {sum(seconds):.1f} s for {len(out)} scenarios, mean {np.mean(seconds):.3f} s, slowest {max(seconds):.2f} s (seed {seeds[int(np.argmax(seconds))]})")
     return out
+
+
+@pytest.fixture(scope="module")
+def slice_(oracle_mod):
+    """every scenario of the first block with the reference's observations and what the driver noted about it; computed once"""
+    return _walk_block(oracle_mod, fc.FIRST_BLOCK)
+
+
+@pytest.fixture(scope="module")
+def slice2(oracle_mod):
+    """the same of the second block (the signed-distance calls)"""
+    return _walk_block(oracle_mod, fc.SECOND_BLOCK)
 
 
 def _features(sc):
@@ -38,6 +53,7 @@ def _features(sc):
     f = collections.Counter()
     script = sc["script"]
     pending, fetched_since_call, ticks_since_call = [], True, 0
+    full, behind_a_call = {}, False          # signed-distance slot -> samples of its table; whether the step before was a call that completes the tick
     for k, (name, a) in enumerate(script):
         f[name] += 1
         f[fc.coverage_name(name, a)] += 1 if fc.coverage_name(name, a) != name else 0
@@ -46,6 +62,22 @@ def _features(sc):
             f["kinematic move twice"] += 1
         if name == "set_heightfield" and fc.coverage_name(prev, script[k - 1][1]) in STATE_CHANGING:
             f["heightfield set right behind a call"] += 1
+        if name == "set_distance_field":
+            count = 27 if a["prop"] == "floor" else a["n"] ** 3
+            f[f"slot {a['slot']}"] += 1; f["prop " + a["prop"]] += 1
+            if a["slot"] in full:
+                f["table replaced, " + ("the same size" if full[a["slot"]] == count else "another size")] += 1
+                f["table replaced right behind a call"] += behind_a_call
+            full[a["slot"]] = count
+        if name == "clear_distance_field":
+            f[f"slot {a['slot']}"] += 1
+            f["slot cleared right behind a call"] += behind_a_call and a["slot"] in full
+            full.pop(a["slot"], None)
+        if name == D:
+            f[f"slot {a['slot']}"] += 1
+            f["collide on a full slot" if a["slot"] in full else "collide on an empty slot"] += 1
+            f["a moving pose"] += any(a["lin"]) and any(a["ang"])
+        behind_a_call = fc.coverage_name(name, a) in STATE_CHANGING or (name == D and a["slot"] in full)
         if name == "apply_impulses":
             for it in a["items"]:
                 f["impulse item " + it[0]] += 1
@@ -71,12 +103,14 @@ def _features(sc):
 
 
 def test_the_slice_is_what_the_gpu_module_runs():
-    assert len(fc.FIXED_SLICE) == fc.N_PAIRS + fc.N_PLANTED + fc.N_RANDOM == 200
+    assert len(fc.FIXED_SLICE) == fc.N_PAIRS + fc.N_PLANTED + fc.N_RANDOM + len(fc.SECOND_BLOCK) == 200 + len(fc.SECOND_BLOCK)
+    assert fc.FIXED_SLICE == fc.FIRST_BLOCK + fc.SECOND_BLOCK and len(fc.FIRST_BLOCK) == 200
+    assert len(fc.SECOND_BLOCK) == fc.N2_PAIRS + fc.N2_PLANTED + fc.N2_LIFETIMES + fc.N2_RANDOM == 21 + 4 + 7 + 48 and len(fc.chunks()) == 25 + 10
     assert [s for c in fc.chunks() for s in c] == list(fc.FIXED_SLICE) and all(len(c) <= fc.CHUNK for c in fc.chunks())
 
 
 def test_a_scenario_is_a_pure_function_of_its_seed_and_prints_as_text():
-    for seed in (0, 57, 123, 150, 199, 12345):
+    for seed in (0, 57, 123, 150, 199, 12345, 200, 220, 224, 228, 231, 250):
         a, b = fc.make_scenario(seed), fc.make_scenario(seed)
         assert a == b and fc.loads(fc.dumps(a)) == a
         assert all(isinstance(step, list) and isinstance(step[0], str) and isinstance(step[1], dict) for step in a["script"])
@@ -142,7 +176,15 @@ def test_contacts_hit_and_forces_move_something(slice_):
 
 
 def test_every_final_state_is_finite_and_moving(slice_):
-    for sc, obs, info in slice_:
+    _finite_and_moving(slice_)
+
+
+def test_second_block_every_final_state_is_finite_and_moving(slice2):
+    _finite_and_moving(slice2)
+
+
+def _finite_and_moving(block):
+    for sc, obs, info in block:
         x, v = info["final"]
         assert np.isfinite(x).all() and np.isfinite(v).all(), sc["seed"]
         assert np.abs(v).max() > 0.05, sc["seed"]
@@ -151,9 +193,9 @@ def test_every_final_state_is_finite_and_moving(slice_):
                 assert np.isfinite(payload).all(), (sc["seed"], lab)
 
 
-def test_every_planted_refusal_is_one_the_reference_refuses(slice_):
+def _refusals_of(block):
     kinds = collections.Counter()
-    for sc, obs, info in slice_:
+    for sc, obs, info in block:
         assert len(info["refusals"]) == 1, sc["seed"]
         what, status = info["refusals"][0]
         assert status is not None and status < 0, (sc["seed"], what)
@@ -163,12 +205,40 @@ def test_every_planted_refusal_is_one_the_reference_refuses(slice_):
         before = [o for o in obs[:k] if o[0] == "counters"]
         assert obs[k + 1][0] == "counters" and (not before or obs[k + 1][2] == before[-1][2]), sc["seed"]
     print("refusals: " + ", ".join(f"{k} {v}" for k, v in sorted(kinds.items())))
+    return kinds
+
+
+def test_every_planted_refusal_is_one_the_reference_refuses(slice_):
+    kinds = _refusals_of(slice_)
     assert len(kinds) >= 5 and min(kinds.values()) >= 5
 
 
+def test_second_block_every_planted_refusal_is_one_the_reference_refuses(slice2):
+    kinds = _refusals_of(slice2)      # (one per scenario, a refusal, changing no counter: asserted in there)
+    assert kinds["distance_field_slot_4"] >= 5 and kinds["distance_field_restitution"] >= 5, kinds
+    for sc, _, _ in slice2:
+        for name, a in sc["script"]:
+            if name == "refuse" and a["what"] == "distance_field_restitution":
+                full = {}
+                for n2, a2 in sc["script"][:sc["script"].index([name, a])]:
+                    if n2 == "set_distance_field":
+                        full[a2["slot"]] = True
+                    elif n2 == "clear_distance_field":
+                        full.pop(a2["slot"], None)
+                assert a["slot"] in full and a["pose"]["restitution"] == 1.5, (sc["seed"], "restitution 1.5 on a FULL slot")
+
+
 def test_replaying_a_printed_script_gives_the_same_observations(slice_, oracle_mod):
-    for k in (3, 36, 64, 117, 150, 199):
-        sc, obs, _ = slice_[k]
+    _replay(slice_, (3, 36, 64, 117, 150, 199), oracle_mod)
+
+
+def test_second_block_replaying_a_printed_script_gives_the_same_observations(slice2, oracle_mod):
+    _replay(slice2, (0, 20, 24, 28, 31, 60), oracle_mod)      # a pair, (D, D), a planted one, two table lifetimes, a random one
+
+
+def _replay(block, picks, oracle_mod):
+    for k in picks:
+        sc, obs, _ = block[k]
         again = fc.run_reference(oracle_mod, fc.loads(fc.dumps(sc)))
         assert fc.first_mismatch(_as_group(obs), _as_group(again)) is None, sc["seed"]
 
@@ -254,3 +324,141 @@ def test_counter_model_calls_that_touch_nothing(oracle_mod):
                     ["clear_heightfield", {}], ["collide_heightfield", {"friction": 0.1, "restitution": 0.0}], step]
     obs = fc.run_reference(oracle_mod, sc)
     assert obs[-1][2] == (3, 0, 0), obs[-1]
+
+
+# ---- the second block: the signed-distance calls (SPEC.md 2i) against everything above ------------------------------------------------------------
+
+def test_the_first_block_is_byte_for_byte_what_it_was():
+    """tests/golden/frame_slice_v1.sha256.txt: one SHA-256 of dumps(make_scenario(seed)) per line for seeds 0 .. 199, written by the commit
+    before the generator learnt the signed-distance steps"""
+    with open(os.path.join(fc.ROOT, "tests", "golden", "frame_slice_v1.sha256.txt")) as fh:
+        want = fh.read().split()
+    assert len(want) == len(fc.FIRST_BLOCK) == 200
+    got = [hashlib.sha256(fc.dumps(fc.make_scenario(seed)).encode()).hexdigest() for seed in fc.FIRST_BLOCK]
+    assert got == want, [seed for seed in fc.FIRST_BLOCK if got[seed] != want[seed]]
+    assert not any(name.endswith("distance_field") for seed in fc.FIRST_BLOCK for name, _ in fc.make_scenario(seed)["script"])
+
+
+def _names_with_slots(sc):
+    """coverage names of a script, D only where its slot holds a table (elsewhere "D on an empty slot": not the call that completes the tick)"""
+    full, out = set(), []
+    for name, a in sc["script"]:
+        if name == "set_distance_field":
+            full.add(a["slot"])
+        elif name == "clear_distance_field":
+            full.discard(a["slot"])
+        out.append((D if a["slot"] in full else "D on an empty slot") if name == D else fc.coverage_name(name, a))
+    return out
+
+
+def test_second_block_every_ordered_pair_with_the_distance_field_call_stands_back_to_back(slice2):
+    seen = set()
+    for sc, _, _ in slice2:
+        names = _names_with_slots(sc)
+        seen |= set(zip(names, names[1:]))
+    pairs = [(p, q) for p in ALL for q in ALL if D in (p, q)]
+    missing = [pq for pq in pairs if pq not in seen]
+    print(f"second block, pair matrix: {len(pairs) - len(missing)} of {len(pairs)} ordered pairs with {D}")
+    assert len(pairs) == 21 and not missing, missing
+    for j, (A, B) in enumerate(fc.DF_PAIRS):       # scenario j of the block is the one that plants pair j, the table set before the first tick
+        sc = slice2[j][0]
+        names = _names_with_slots(sc)
+        assert (A, B) in set(zip(names, names[1:])), (j, A, B)
+        assert names.index("set_distance_field") < names.index("step"), j
+        if (A, B) == (D, D):
+            k = list(zip(names, names[1:])).index((D, D))
+            assert sc["script"][k][1]["slot"] != sc["script"][k + 1][1]["slot"], "two different slots"
+
+
+def test_second_block_the_distance_field_call_meets_every_left_state_and_every_tick_shape(slice2):
+    left, shape = set(), set()
+    for _, _, info in slice2:
+        left |= set(info["call_left"]); shape |= set(info["call_shape"])
+    missing = [(D, s) for s in LEFT_STATES if (D, s) not in left] + [(D, s) for s in TICK_SHAPES if (D, s) not in shape]
+    assert not missing, missing
+    for k in range(fc.N2_PLANTED):                 # ... and the planted scenarios are the ones that say so
+        info = slice2[fc.N2_PAIRS + k][2]
+        assert (D, LEFT_STATES[k]) in info["call_left"] and (D, TICK_SHAPES[(k + 1) % 4]) in info["call_shape"], k
+
+
+def test_second_block_every_step_occurs_often_enough(slice2):
+    total = collections.Counter()
+    for sc, _, _ in slice2:
+        total += _features(sc)
+    print("steps of the second block: " + ", ".join(f"{k} {v}" for k, v in sorted(total.items())))
+    names = ["set_distance_field", "clear_distance_field", "collide_distance_field", "table replaced right behind a call", "collide on an empty slot",
+             "slot cleared right behind a call", "slot 0", "slot 1", "slot 2", "slot 3", "prop sphere", "prop floor", "a moving pose"]
+    few = {k: total[k] for k in names if total[k] < 10}
+    assert not few, few
+    assert total["table replaced, the same size"] >= 5 and total["table replaced, another size"] >= 5, "the memory written over, and released"
+    assert total["refuse"] == len(slice2), "one refusal per scenario"
+    sizes = {a["n"] for sc, _, _ in slice2 for name, a in sc["script"] if name == "set_distance_field" and a["prop"] == "sphere"}
+    assert sizes == {9, 17}
+    axes = collections.Counter()
+    for sc, _, _ in slice2:
+        axes[sc["body"]] += 1; axes[sc["mode"]] += 1
+        for k in ("peek0", "graph", "uvs", "every_tick"):
+            axes[f"{k}={sc[k]}"] += 1
+    print("axes of the second block: " + ", ".join(f"{k} {v}" for k, v in sorted(axes.items())))
+    assert all(axes[k] >= 8 for k in list(fc.BODIES) + ["full", "render_set", "embedding"] + [f"{k}={v}" for k in ("peek0", "graph", "uvs", "every_tick") for v in (True, False)]), axes
+
+
+def test_second_block_distance_field_contacts_hit(slice2):
+    with_calls = [info for sc, _, info in slice2 if D in _names_with_slots(sc)]
+    hit = sum(1 for info in with_calls if any(h > 0 for h in info["distance_field_hits"]))
+    calls = [h for info in with_calls for h in info["distance_field_hits"]]
+    print(f"signed-distance contacts: a non-empty hit mask in {hit} of {len(with_calls)} scenarios, in {sum(h > 0 for h in calls)} of {len(calls)} calls on a full slot")
+    assert len(with_calls) >= fc.N2_PAIRS + fc.N2_PLANTED + fc.N2_LIFETIMES and 2 * hit >= len(with_calls)      # (every written scenario has such a call)
+    for sc, _, info in slice2:                      # the list is the signed-distance calls' alone, one entry per call on a full slot
+        assert len(info["distance_field_hits"]) == _names_with_slots(sc).count(D), sc["seed"]
+
+
+def test_second_block_the_steps_listed_as_leaving_the_tick_held_back_do(slice2):
+    """the table-lifetime scenarios name the steps that must not complete the tick: behind each, with nothing but such steps and table
+    sets between, the next tick fuses -- which is what the GPU's ticks_fused is compared with"""
+    listed = 0
+    for k in range(fc.N2_LIFETIMES):
+        sc, obs, _ = slice2[fc.N2_PAIRS + fc.N2_PLANTED + k]
+        assert sc["plan"] == "table lifetime: " + fc.DF_LIFETIMES[k]
+        counters = [o[2] for o in obs if o[0] == "counters"]
+        assert len(counters) == len(sc["script"])
+        for at in sc["leaves_held_back"]:
+            assert sc["script"][at][0] in ("set_distance_field", "clear_distance_field", D), (sc["seed"], at)
+            nxt = at + 1
+            while sc["script"][nxt][0] != "step":
+                assert nxt in sc["leaves_held_back"], (sc["seed"], at, "something else stands between the step and the next tick")
+                nxt += 1
+            assert sc["script"][at - 1][0] == "step" or at - 1 in sc["leaves_held_back"], (sc["seed"], at, "the tick is not held back in front of the step")
+            assert counters[at] == counters[at - 1] and counters[nxt][0] == counters[at][0] + 1, (sc["seed"], at, "the next tick does not fuse")
+            listed += 1
+    names = lambda k: _names_with_slots(slice2[fc.N2_PAIRS + fc.N2_PLANTED + k][0])      # noqa: E731
+    assert listed >= 8
+    assert "D on an empty slot" in names(3) and "D on an empty slot" in names(4)
+    f = names(5)                                   # colliders, terrain, then props: one slot at two poses, then a second slot
+    k = f.index("collide_with_reactions")
+    assert f[k:k + 5] == ["collide_with_reactions", "collide_heightfield", D, D, D]
+    a = [s[1] for s in slice2[fc.N2_PAIRS + fc.N2_PLANTED + 5][0]["script"][k + 2:k + 5]]
+    assert a[0]["slot"] == a[1]["slot"] != a[2]["slot"] and a[0]["centre"] != a[1]["centre"]
+    g = [n for n, _ in slice2[fc.N2_PAIRS + fc.N2_PLANTED + 6][0]["script"]]
+    k = g.index("readback_begin")
+    assert g[k:k + 5] == ["readback_begin", D, "readback_end", "raycast", "closest_points"]
+
+
+def test_counter_model_distance_field_slots(oracle_mod):
+    s = ("step", 0.02, 6)
+    assert _walk(TickModel(peeking=False), [s, ("set_distance_field", 1), s]) == (1, 0, 0), "a set completes nothing"
+    assert _walk(TickModel(peeking=False), [s, ("set_distance_field", 1), s, ("collide_distance_field", 1), s, s]) == (2, 0, 0), "a call on a full slot completes the tick"
+    assert _walk(TickModel(peeking=False), [s, ("set_distance_field", 1), s, ("collide_distance_field", 2), s, s]) == (3, 0, 0), "a call on an empty slot does nothing"
+    assert _walk(TickModel(peeking=False), [s, ("set_distance_field", 1), ("set_distance_field", 1), ("clear_distance_field", 1), ("collide_distance_field", 1), s]) == (1, 0, 0)
+    assert _walk(TickModel(peeking=False), [s, ("kinematic",), ("collide_distance_field", 0), s]) == (1, 1, 0), "... and leaves a pending move pending"
+    assert _walk(TickModel(peeking=False), [s, ("set_distance_field", 0), ("kinematic",), ("collide_distance_field", 0), s, s]) == (1, 0, 0), "a call on a full slot lands it"
+    # in the driver: the twin of the heightfield script above
+    sc = dict(fc.make_scenario(0))
+    step = ["step", {"dt": 0.02, "S": 6}]
+    call = [D, {"slot": 2, "centre": [7.5, -3.0, 7.5], "quat": [0, 0, 0, 1], "lin": [0, 0, 0], "ang": [0, 0, 0], "friction": 0.1, "restitution": 0.0}]
+    table = ["set_distance_field", {"slot": 2, "prop": "sphere", "radius": 4.5, "n": 9, "thickness": 2.7}]
+    sc["script"] = [step, call, step, table, step, call, step, ["clear_distance_field", {"slot": 2}], call, step]
+    info = {}
+    obs = fc.run_reference(oracle_mod, sc, info=info)
+    assert obs[-1][2] == (3, 0, 0), obs[-1]
+    assert len(info["distance_field_hits"]) == 1 and info["distance_field_hits"][0] > 0 and info["call_left"] == [(D, LEFT_STATES[1])]

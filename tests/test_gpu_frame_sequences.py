@@ -4,7 +4,7 @@ its kind: positions, velocities, snapshot arrays, boxes and hits bitwise, body-s
 exact counts, refusals by their status, and sb_stats' ticks_fused / ticks_fused_kinematic / readback_peeks after every step against the
 counter model. tests/test_frame_sequences.py asserts on the CPU that the fixed slice covers what it claims to.
 
-a. one rank: the fixed slice, in chunks        b. 2 and 4 ranks, both host models, whole meshes and windows (tests/frame_group_case.py)
+a. one rank: the fixed slice, in chunks -- 25 of the first block, 10 of the second (the signed-distance calls, SPEC.md 2i)        b. 2 and 4 ranks, both host models, whole meshes and windows (tests/frame_group_case.py)
 c. twins: reactions fetched at once and after the next tick -- the same bits throughout, ticks_fused as the model predicts for each"""
 import functools
 import os
@@ -66,7 +66,7 @@ def test_one_rank_walks_the_fixed_slice_like_the_reference(chunk):
 def _twin_seeds():
     """scenarios of the slice that fetch reactions right behind the call, a tick following: their twins fetch behind that tick"""
     out = []
-    for seed in fc.FIXED_SLICE:
+    for seed in fc.FIRST_BLOCK:
         names = [n for n, _ in fc.make_scenario(seed)["script"]]
         at = [k for k, n in enumerate(names) if n == "collider_reactions" and names[k - 1] == "collide_with_reactions"]
         if at and "step" in names[at[0]:]:
